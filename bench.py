@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """AES-GCM seal+open throughput of the MI355X record engine (BASELINE.json metric), device-resident.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload tls16k]
-                    [--extra quic1200,mixed,mixedrand,shard1200,ptlsbench,quic64k,tls64k] [--no-cpu-baseline] [--no-e2e]
+    python bench.py [--gpus N --steps K --warmup W] [--workload tls16k] [--dump-outputs DIR]
+    python bench.py --full [--extra quic1200,mixed,mixedrand,shard1200,ptlsbench,quic64k,tls64k] [--no-cpu-baseline]
+                    [--no-e2e]
 
 One step = seal the whole batch, then open the sealed batch again (one launch each), inputs already in HBM.
 value = (sum L sealed + sum L opened) over all ranks / max-over-ranks wall time of the K timed steps, in GiB/s
@@ -12,9 +13,16 @@ and relays rank 0's line. The headline workload is weak scaling (every rank seal
 shard1200 leg (configs[4]: 32M x 1200 B split across the ranks) is strong scaling. Independent record shards, no
 collective on the data path; a barrier + max/sum reductions of the timings only.
 
-Also reported:
+A plain run does what `value` needs and no more: it sets the headline workload up, warms up, times the K steps
+(ms_per_step = wall time of the timed steps / K), checks the round trip on the device, writes --dump-outputs and prints
+the line. Reported from those same steps:
   roofline      dominant kernel (seal), algorithmic bytes per launch / average launch time (HIP events on the
                 launch stream) against the 8 TB/s HBM peak of MI355X; traffic (PMC) from profiles/ when committed
+
+--dump-outputs DIR writes what the last timed step left in the output arenas as DIR/<name>.npy (dump_outputs below;
+same arguments, same inputs, so two builds can be compared file by file).
+
+Only with --full (everything that takes runs of its own):
   cpu_baseline  picotls' own lib/fusion.c (oracle/_ref, compiled from the reference) sealing+opening a bounded sample
                 of each workload on this host's cores (rank 0, N=1 only): ptls_fusion_aes{128,256}gcm (the ptlsbench
                 path, primary) and ptls_non_temporal_aes128gcm (the TLS path, secondary), median of reps with the
@@ -52,8 +60,14 @@ def parse():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--workload", default="tls16k")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline: --extra workloads, e2e_host_buffers, cpu_baseline and "
+                        "the fusion spot checks (a plain run times the headline workload only)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step (sampled records, per-block byte sums, ok bytes) as "
+                        "DIR/<name>.npy")
     p.add_argument("--extra", default="quic1200,mixed,mixedrand,shard1200,ptlsbench,quic64k,tls64k",
-                   help="comma list of extra workloads to report ('' for none)")
+                   help="--full: comma list of extra workloads to report ('' for none)")
     p.add_argument("--records", type=int, default=0, help="override record count (smaller runs)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=3.0, help="wall budget of each cpu_baseline leg")
@@ -64,8 +78,14 @@ def parse():
                    help="--e2e: chunks of the pipelined mode (16 MiB at the default 4 GiB: 34.4 GiB/s vs 31.6-31.8 with 64-16)")
     p.add_argument("--schedule", default="auto", choices=["auto", "lockstep", "chunked"],
                    help="batch schedule (ptls_mi355x_keyset_set_schedule)")
-    p.add_argument("--verify", type=int, default=1, help="verify round trip + fusion spot checks after timing")
-    return p.parse_args()
+    p.add_argument("--verify", type=int, default=1,
+                   help="verify the round trip after timing (with --full also the fusion spot checks)")
+    args = p.parse_args()
+    if args.e2e and not args.full:
+        p.error("--e2e is a --full leg")
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(gpus: int):
@@ -119,7 +139,10 @@ def make_rank(gpus: int):
                                 always=os.environ.get("PTLS_BENCH_PROCESS_GROUP") == "1")
 
 
-def run_workload(R, wl, steps: int, warmup: int, verify: int, shard_global: bool, schedule: str = "auto"):
+def run_workload(R, wl, steps: int, warmup: int, verify: int, shard_global: bool, schedule: str = "auto",
+                 sample: bool = True, dump_dir=None):
+    """One leg: set up, warm up, time `steps` seal+open steps. sample: keep host copies of a few records for the fusion
+    spot check (the cpu_baseline leg of --full). dump_dir: write the last step's outputs there (dump_outputs)."""
     import torch
     import picotls_amd as pa
     from picotls_amd.records import algorithmic_bytes
@@ -142,7 +165,9 @@ def run_workload(R, wl, steps: int, warmup: int, verify: int, shard_global: bool
     d_aad = torch.from_numpy(wl.aad_arena(b, begin)).to(dev)
     d_pt = payload_torch(wl.seed + 7919 * (R.rank if not shard_global else 0), b.pt_bytes, dev)
     zero_slot_padding(d_pt, b.seal, dev)  # so the round-trip check can compare whole arenas
-    d_sealed = torch.empty(b.sealed_bytes, dtype=torch.uint8, device=dev)
+    # (zeroed, not empty: the bytes between sealed records of other lengths than 16k are no kernel's to write, and
+    # --dump-outputs sums whole blocks of the arena)
+    d_sealed = torch.zeros(b.sealed_bytes, dtype=torch.uint8, device=dev)
     d_back = torch.zeros(b.pt_bytes, dtype=torch.uint8, device=dev)
     d_ok = torch.zeros(b.n, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev)
@@ -201,7 +226,10 @@ def run_workload(R, wl, steps: int, warmup: int, verify: int, shard_global: bool
         same = bool(torch.equal(d_back, d_pt))
         res["verified_roundtrip"] = R.sum(float(ok_all and same)) == R.world  # every rank's shard round-trips
         # records for the bit-exact fusion check, which runs in the cpu_baseline leg (rank 0)
-        res["sample"] = collect_sample(wl, b, keys, ivs, d_pt, d_aad, d_sealed, d_back, d_ok) if R.rank == 0 else None
+        res["sample"] = (collect_sample(wl, b, keys, ivs, d_pt, d_aad, d_sealed, d_back, d_ok)
+                         if sample and R.rank == 0 else None)
+    if dump_dir:
+        res["dumped"] = dump_outputs(dump_dir, R.rank, b, d_sealed, d_back, d_ok)
     del d_pt, d_sealed, d_back, d_ok, d_seal, d_open, d_aad
     ks.free()
     torch.cuda.empty_cache()
@@ -246,6 +274,86 @@ def zero_slot_padding(arena, recs, dev):
     for p in range(15):
         sel = starts[padt > p] + p
         arena[sel] = 0
+
+
+DUMP_SAMPLE_RECS = 192  # x (16384 + 16) B x 4 (float32) x 2 arenas = 25 MB at the longest records
+DUMP_MAX_BLOCKS = 1 << 20  # byte sums per arena, float64: 8 MB each
+DUMP_MAX_OK = 1 << 21  # ok bytes kept whole up to this many records (float32: 8 MB)
+
+
+def _block_sums(t, max_blocks: int = DUMP_MAX_BLOCKS, piece: int = 1 << 30):
+    """Sums of the bytes of t over consecutive blocks (a power of two of at least 4096 bytes, at most max_blocks of them,
+    the last one short), on the device, a piece of the arena at a time. Returns (float64 sums, block size)."""
+    import torch
+
+    n, block = t.numel(), 4096
+    while (n + block - 1) // block > max_blocks:
+        block *= 2
+    piece = max(piece // block, 1) * block
+    parts = []
+    for lo in range(0, n, piece):
+        x = t[lo:lo + piece]
+        whole = x.numel() // block
+        if whole:
+            parts.append(x[:whole * block].view(whole, block).sum(dim=1, dtype=torch.int64))
+        if x.numel() > whole * block:  # (the arena's tail)
+            parts.append(x[whole * block:].sum(dtype=torch.int64).reshape(1))
+    sums = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=t.device)
+    return sums.cpu().numpy().astype(np.float64), block
+
+
+def dump_outputs(path: str, rank: int, b, d_sealed, d_back, d_ok) -> dict:
+    """--dump-outputs: what a caller of the timed path holds after its last step, i.e. the sealed arena (ciphertext ||
+    tag per record), the arena the open wrote the plaintext back into and the ok byte of every record, as .npy files
+    of at most ~50 MB together (rank 0: <name>.npy; rank r > 0 of a multi-GPU run: <name>_rank<r>.npy):
+
+      sample_index      float64  the sampled records: the first, the last and DUMP_SAMPLE_RECS drawn with a fixed seed
+      sealed_sample     float32  their sealed bytes (len + 16 each), concatenated in sample_index order
+      opened_sample     float32  their opened plaintext bytes (len each), concatenated
+      sealed_blocksum   float64  byte sums over consecutive blocks of the whole sealed arena (every record counts)
+      opened_blocksum   float64  the same over the opened arena
+      block_bytes       float64  [block size of sealed_blocksum, of opened_blocksum]
+      ok                float32  every record's ok byte (batches of up to DUMP_MAX_OK records), or
+      ok_sample, ok_sum float32 / float64  the sampled records' ok bytes and [sum of all ok bytes, records]
+    """
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    dev = d_sealed.device
+    files = {}
+    if b.n:
+        rng = np.random.default_rng(0x0D15EA5E)
+        idx = np.unique(np.concatenate([[0, b.n - 1], rng.integers(0, b.n, DUMP_SAMPLE_RECS)])).astype(np.int64)
+    else:
+        idx = np.zeros(0, np.int64)
+    sub = b.seal[idx]
+    lens = sub["len"].astype(np.int64)
+
+    def gather(arena, offs, sizes):
+        # byte positions of the sampled records, one device gather per arena
+        total = int(sizes.sum())
+        if not total:
+            return np.zeros(0, np.float32)
+        starts = np.repeat(offs - np.concatenate([[0], np.cumsum(sizes)[:-1]]), sizes)
+        pos = torch.from_numpy(starts + np.arange(total, dtype=np.int64)).to(dev)
+        return arena[pos].cpu().numpy().astype(np.float32)
+
+    files["sample_index"] = idx.astype(np.float64)
+    files["sealed_sample"] = gather(d_sealed, sub["out_off"].astype(np.int64), lens + 16)
+    files["opened_sample"] = gather(d_back, sub["in_off"].astype(np.int64), lens)  # (the open writes at the seal's in_off)
+    files["sealed_blocksum"], sb = _block_sums(d_sealed)
+    files["opened_blocksum"], ob = _block_sums(d_back)
+    files["block_bytes"] = np.array([sb, ob], np.float64)
+    if b.n <= DUMP_MAX_OK:
+        files["ok"] = d_ok.cpu().numpy().astype(np.float32)
+    else:
+        files["ok_sample"] = d_ok[torch.from_numpy(idx).to(dev)].cpu().numpy().astype(np.float32)
+        files["ok_sum"] = np.array([float(d_ok.sum(dtype=torch.int64).item()), float(b.n)], np.float64)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in files.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+    return {"dir": path, "files": sorted(n + suffix + ".npy" for n in files),
+            "bytes": int(sum(a.nbytes for a in files.values()))}
 
 
 def collect_sample(wl, b, keys, ivs, d_pt, d_aad, d_sealed, d_back, d_ok, nsample: int = 64):
@@ -703,7 +811,10 @@ def main():
     if args.records:
         wl = wl.scaled(args.records)
     shard_global = args.workload == "shard1200"
-    res = run_workload(R, wl, args.steps, args.warmup, args.verify, shard_global, args.schedule)
+    # the fusion spot checks run in the cpu_baseline leg (rank 0, N = 1, --full): records are sampled only for it
+    cpu_leg = args.full and R.rank == 0 and R.world == 1 and not args.no_cpu_baseline
+    res = run_workload(R, wl, args.steps, args.warmup, args.verify, shard_global, args.schedule, sample=cpu_leg,
+                       dump_dir=args.dump_outputs)
 
     value, wall = aggregate_throughput(R, res["payload_bytes"], res["wall_s"], args.steps)
     seal_s, open_s = res["seal_ms"] / 1e3, res["open_ms"] / 1e3
@@ -715,6 +826,7 @@ def main():
         "n_gpus": R.world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(wall / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "strong" if shard_global else "weak",
@@ -750,7 +862,9 @@ def main():
     samples = {wl.name: res.get("sample")}
     extra = {}
     ptlsbench_gpu = None
-    for name in [x for x in args.extra.split(",") if x]:
+    if res.get("dumped"):
+        out["dumped_outputs"] = res["dumped"]
+    for name in [x for x in args.extra.split(",") if x] if args.full else []:
         if name == args.workload:
             continue
         if name == "ptlsbench":
@@ -768,7 +882,7 @@ def main():
         w2 = WORKLOADS[name]
         if args.records:
             w2 = w2.scaled(max(1, args.records * (wl.rec_len or 8192) // (w2.rec_len or 8192)))
-        r2 = run_workload(R, w2, args.steps, args.warmup, args.verify, name == "shard1200", args.schedule)
+        r2 = run_workload(R, w2, args.steps, args.warmup, args.verify, name == "shard1200", args.schedule, sample=cpu_leg)
         samples[name] = r2.get("sample")
         v2, _ = aggregate_throughput(R, r2["payload_bytes"], r2["wall_s"], args.steps)
         extra[name] = {"value": round(v2, 3), "unit": "GiB/s", "desc": w2.desc,
@@ -789,10 +903,10 @@ def main():
             extra[name]["per_rank"] = per_rank(R, r2)
     if extra:
         out["extra"] = extra
-    if args.e2e or (args.e2e is None and R.world == 1 and not args.records):  # (N = 1 at full size: 12 GiB pinned)
+    if args.full and (args.e2e or (args.e2e is None and R.world == 1 and not args.records)):  # (N = 1 at full size: 12 GiB pinned)
         out["e2e_host_buffers"] = run_e2e(R, WORKLOADS[args.workload].scaled(min(wl.nrecs, max(1, (4 << 30) // (wl.rec_len or 8192)))), args.e2e_chunks,
                                           schedule=args.schedule)
-    if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
+    if cpu_leg:
         out["cpu_baseline"], checks = cpu_baseline(wl, args.cpu_seconds, samples if args.verify else {}, ptlsbench_gpu)
         cb = out["cpu_baseline"]
         if cb.get("value"):  # GPU / CPU, against the noisy 16-thread median and against the stable 1-thread x cores

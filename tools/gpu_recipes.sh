@@ -281,9 +281,10 @@ exit 0
 full)
   # full measurement session: default bench (+e2e), the many-key config and the 32M x 1200 B config on one GPU
   (
-timeout -k 10 600 python bench.py --e2e > gpurun_out/bench_default.log 2>&1
-rc=$?; echo "bench default rc=$rc"; grep "^{" gpurun_out/bench_default.log | tail -1 | cut -c1-3000
-[ $rc -ne 0 ] && { tail -20 gpurun_out/bench_default.log; exit $rc; }
+out=${BENCH_OUT:-bench_out}; mkdir -p "$out"
+timeout -k 10 600 python bench.py --full --e2e > "$out/bench_default.log" 2>&1
+rc=$?; echo "bench default rc=$rc"; grep "^{" "$out/bench_default.log" | tail -1 | cut -c1-3000
+[ $rc -ne 0 ] && { tail -20 "$out/bench_default.log"; exit $rc; }
 timeout -k 10 600 python bench.py --workload mixed --extra= --no-cpu-baseline --steps 3 --warmup 1 > gpurun_out/bench_mixed.log 2>&1
 rc=$?; echo "bench mixed rc=$rc"; grep "^{" gpurun_out/bench_mixed.log | tail -1 | cut -c1-1500
 [ $rc -ne 0 ] && { tail -20 gpurun_out/bench_mixed.log; exit $rc; }
@@ -448,9 +449,10 @@ round3)
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "$@" > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc"; grep -E "FAILED|ERROR" gpurun_out/pytest_gpu.log | tail -30; tail -3 gpurun_out/pytest_gpu.log
 [ $rc -ne 0 ] && { tail -80 gpurun_out/pytest_gpu.log; exit $rc; }
-timeout -k 10 600 python bench.py > gpurun_out/bench_default.log 2> gpurun_out/bench_default.err
-rc=$?; echo "bench rc=$rc"; tail -c 3000 gpurun_out/bench_default.log
-[ $rc -ne 0 ] && { tail -30 gpurun_out/bench_default.err; exit $rc; }
+out=${BENCH_OUT:-bench_out}; mkdir -p "$out"
+timeout -k 10 600 python bench.py --full > "$out/bench_default.log" 2> "$out/bench_default.err"
+rc=$?; echo "bench rc=$rc"; tail -c 3000 "$out/bench_default.log"
+[ $rc -ne 0 ] && { tail -30 "$out/bench_default.err"; exit $rc; }
 timeout -k 10 300 python tools/hp_cost.py --rounds 7 > gpurun_out/hp_cost.txt 2>&1; rc=$?; grep hp_cost gpurun_out/hp_cost.txt; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python tools/small_batch.py --rounds 3 > gpurun_out/small_batch.txt 2>&1; rc=$?; grep -v amdgpu gpurun_out/small_batch.txt | head -8
 exit $rc
