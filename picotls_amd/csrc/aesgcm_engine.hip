@@ -179,17 +179,10 @@ static int set_kernel_attrs(void)
     HIP_TRY(hipFuncSetAttribute((const void *)gcm_batch_kernel<10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALLOC));
     HIP_TRY(hipFuncSetAttribute((const void *)gcm_batch_kernel<14, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALLOC));
     HIP_TRY(hipFuncSetAttribute((const void *)gcm_batch_kernel<14, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_ALLOC));
-#if SEG_COOP  // (one instantiation for both settings, launch_chunked_x)
+    // (the CT template argument is instantiated true only, launch_chunked_x)
 #define CHUNKED_ATTR_X(nr, open, frame, ext)                                                                           \
     HIP_TRY(hipFuncSetAttribute((const void *)gcm_chunked_kernel<nr, open, frame, true, ext>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 CLDS_ALLOC))
-#else
-#define CHUNKED_ATTR_X(nr, open, frame, ext)                                                                           \
-    HIP_TRY(hipFuncSetAttribute((const void *)gcm_chunked_kernel<nr, open, frame, false, ext>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                CLDS_ALLOC));                                                                              \
-    HIP_TRY(hipFuncSetAttribute((const void *)gcm_chunked_kernel<nr, open, frame, true, ext>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                CLDS_ALLOC))
-#endif
 #define CHUNKED_ATTR(nr, open, frame) CHUNKED_ATTR_X(nr, open, frame, 0)
     CHUNKED_ATTR_X(10, false, 0, 1);
     CHUNKED_ATTR_X(10, true, 0, 1);
@@ -197,15 +190,12 @@ static int set_kernel_attrs(void)
     CHUNKED_ATTR_X(14, true, 0, 1);
     CHUNKED_ATTR_X(10, false, 0, 2);
     CHUNKED_ATTR_X(14, false, 0, 2);
-#if MK_RUNS  // (round 6) the serial W8 kernel of many-key batches, with multi-key runs (EXT 5)
+    // (round 6) the serial W8 kernel of many-key batches, with multi-key runs (EXT 5)
 #define CHUNKED_ATTR_MK(frame)                                                                                         \
     CHUNKED_ATTR_X(10, false, frame, 5);                                                                               \
     CHUNKED_ATTR_X(10, true, frame, 5);                                                                                \
     CHUNKED_ATTR_X(14, false, frame, 5);                                                                               \
     CHUNKED_ATTR_X(14, true, frame, 5)
-#else
-#define CHUNKED_ATTR_MK(frame) (void)0
-#endif
 #define CHUNKED_ATTR_W8(frame)                                                                                         \
     CHUNKED_ATTR_X(10, false, frame, 3);                                                                               \
     CHUNKED_ATTR_X(10, true, frame, 3);                                                                                \
@@ -216,14 +206,11 @@ static int set_kernel_attrs(void)
     CHUNKED_ATTR_X(14, false, frame, 4);                                                                               \
     CHUNKED_ATTR_X(14, true, frame, 4);                                                                                \
     CHUNKED_ATTR_MK(frame)
-#if W8_HORNER
     CHUNKED_ATTR_W8(0);
     CHUNKED_ATTR_W8(1);
-#if W8_TLS12
     CHUNKED_ATTR_W8(2);
-#endif
-#endif
 #undef CHUNKED_ATTR_W8
+#undef CHUNKED_ATTR_MK
     CHUNKED_ATTR(10, false, 0);
     CHUNKED_ATTR(10, true, 0);
     CHUNKED_ATTR(14, false, 0);
@@ -243,14 +230,8 @@ static int set_kernel_attrs(void)
     HIP_TRY(hipFuncSetAttribute((const void *)hp_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_AES_BYTES));
     HIP_TRY(hipFuncSetAttribute((const void *)hp_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_AES_BYTES));
     HIP_TRY(hipFuncSetAttribute((const void *)quiclb_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_AES_BYTES));
-#if SEG_COOP
 #define SPAN_ATTR(nr, open)                                                                                            \
     HIP_TRY(hipFuncSetAttribute((const void *)gcm_span_kernel<nr, open, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SPAN_LDS))
-#else
-#define SPAN_ATTR(nr, open)                                                                                            \
-    HIP_TRY(hipFuncSetAttribute((const void *)gcm_span_kernel<nr, open, false>, hipFuncAttributeMaxDynamicSharedMemorySize, SPAN_LDS)); \
-    HIP_TRY(hipFuncSetAttribute((const void *)gcm_span_kernel<nr, open, true>, hipFuncAttributeMaxDynamicSharedMemorySize, SPAN_LDS))
-#endif
     SPAN_ATTR(10, false);
     SPAN_ATTR(10, true);
     SPAN_ATTR(14, false);
@@ -285,7 +266,7 @@ static DeviceState *device_state(int dev)
     ds->stage_coherent = !(coh != nullptr && strcmp(coh, "0") == 0);
     const char *ct = getenv("PTLS_MI355X_CONSTANT_TIME");
     // (round 4) every keyset constant-time unless PTLS_MI355X_CONSTANT_TIME=0: since the window-major segment ends
-    // (SEG_COOP) both modes run the same code, whose LDS accesses have data-independent bank patterns, at the same
+    // both modes run the same code, whose LDS accesses have data-independent bank patterns, at the same
     // rate; the flag only keeps such keysets off the lockstep schedule
     ds->ct_default = !(ct != nullptr && strcmp(ct, "0") == 0);
     const char *comb = getenv("PTLS_MI355X_COMBINE");
@@ -559,7 +540,7 @@ struct st_ptls_mi355x_keyset_t {
     size_t spread_cap;  // its bytes (sized for the batches seen so far, spread_bytes)
     hipStream_t spread_stream;
     bool spread_used;
-    // W8 launch pairs (launch_chunked, W8_HORNER): one word per workgroup from the pair's first kernel to its second,
+    // W8 launch pairs (launch_chunked): one word per workgroup from the pair's first kernel to its second,
     // one buffer per stream (allocated on the stream's first pair; a stream orders its own pairs), so that pairs on
     // several streams run concurrently; at most W8_FLAG_STREAMS, the oldest taken over by a new stream in stream order
     std::vector<std::pair<hipStream_t, u32 *>> w8flags;
@@ -1027,37 +1008,29 @@ int ptls_mi355x_keyset_set_iv(ptls_mi355x_keyset_t *ks, size_t key_idx, const vo
 // 784 vs 751 on 1200 B), and its chunked runs balance mixed lengths and short key runs.
 static bool use_chunked(int schedule) { return schedule != PTLS_MI355X_SCHEDULE_LOCKSTEP; }
 
-// Since the window-major segment ends (SEG_COOP) the constant-time template argument changes no instruction of the
-// chunked and span kernels: every keyset, constant-time or not, launches the CT instantiation, so the
-// code object holds one set of these kernels
+// Since the window-major segment ends the constant-time template argument changes no instruction of the chunked and
+// span kernels: every keyset, constant-time or not, launches the CT instantiation, the only one in the
+// code object
 template <int NR, bool OPEN, int FRAME, int EXT = 0>
-static void launch_chunked_x(bool ct, unsigned grid, hipStream_t s, const BatchArgs &a)
+static void launch_chunked_x(unsigned grid, hipStream_t s, const BatchArgs &a)
 {
     COUNT_LAUNCH(EXT == 5 ? 4 : EXT);  // (the MK form of the serial W8 kernel counts as it)
-#if SEG_COOP
-    (void)ct;
     gcm_chunked_kernel<NR, OPEN, FRAME, true, EXT><<<grid, ENGINE_WG, CLDS_ALLOC, s>>>(a);
-#else
-    if (ct)
-        gcm_chunked_kernel<NR, OPEN, FRAME, true, EXT><<<grid, ENGINE_WG, CLDS_ALLOC, s>>>(a);
-    else
-        gcm_chunked_kernel<NR, OPEN, FRAME, false, EXT><<<grid, ENGINE_WG, CLDS_ALLOC, s>>>(a);
-#endif
 }
 
 // the instantiation for the launch: unframed batches with a spread plan (EXT 1) or header-protection masks (EXT 2)
 // have their own (gcm_chunked_kernel)
 template <int NR, bool OPEN, int FRAME>
-static void launch_chunked(bool ct, unsigned grid, hipStream_t s, const BatchArgs &a)
+static void launch_chunked(unsigned grid, hipStream_t s, const BatchArgs &a)
 {
     if constexpr (FRAME == 0) {
         if (a.spread) {
-            launch_chunked_x<NR, OPEN, 0, 1>(ct, grid, s, a);
+            launch_chunked_x<NR, OPEN, 0, 1>(grid, s, a);
             return;
         }
         if constexpr (!OPEN) {
             if (a.hp != nullptr) {
-                launch_chunked_x<NR, false, 0, 2>(ct, grid, s, a);
+                launch_chunked_x<NR, false, 0, 2>(grid, s, a);
                 return;
             }
         }
@@ -1068,27 +1041,25 @@ static void launch_chunked(bool ct, unsigned grid, hipStream_t s, const BatchArg
     // other's runs and EXT 3 returning at once in the workgroups where EXT 4 saw none (BatchArgs::w8_split, w8_flags).
     // A batch of fewer than WHOLE_MIN_RECS records per workgroup in contiguous ranges holds no whole-record run: EXT 4
     // alone. Not for a per-record launch (it publishes completion words, and its 1-16-step units suit the 4-bit path),
-    // nor a batch of fewer than W8_MIN_RECS records (the table build is not repaid). TLS 1.2 framing only with W8_TLS12
-    // (on: faster despite EXT 4's 96-byte-per-lane seal spill, common.h).
-    if constexpr (W8_HORNER && (FRAME != 2 || W8_TLS12)) {
-        if (!a.one_inline && a.done_flag == nullptr && a.nrecs >= W8_MIN_RECS) {
-            const bool whole_possible = a.chunk != 0 || a.bounds != nullptr || (a.nrecs + grid - 1) / grid >= WHOLE_MIN_RECS;
-            BatchArgs b = a;
-            b.w8_split = whole_possible ? 2u : 1u;
-            if (!whole_possible)
-                b.w8_flags = nullptr;
-            // (round 6) many-key batches take EXT 5: EXT 4 plus multi-key runs (gcm_kernels.h scan_mk); one-key batches
-            // keep EXT 4, whose code the MK path would grow (small launches slowed by 5-14 % with it compiled in)
-            if (MK_RUNS && a.multi_key)
-                launch_chunked_x<NR, OPEN, FRAME, 5>(ct, grid, s, b);
-            else
-                launch_chunked_x<NR, OPEN, FRAME, 4>(ct, grid, s, b);
-            if (whole_possible)
-                launch_chunked_x<NR, OPEN, FRAME, 3>(ct, grid, s, b);
-            return;
-        }
+    // nor a batch of fewer than W8_MIN_RECS records (the table build is not repaid). TLS 1.2 framing too (faster despite
+    // EXT 4's 96-byte-per-lane seal spill, common.h).
+    if (!a.one_inline && a.done_flag == nullptr && a.nrecs >= W8_MIN_RECS) {
+        const bool whole_possible = a.chunk != 0 || a.bounds != nullptr || (a.nrecs + grid - 1) / grid >= WHOLE_MIN_RECS;
+        BatchArgs b = a;
+        b.w8_split = whole_possible ? 2u : 1u;
+        if (!whole_possible)
+            b.w8_flags = nullptr;
+        // (round 6) many-key batches take EXT 5: EXT 4 plus multi-key runs (gcm_kernels.h scan_mk); one-key batches
+        // keep EXT 4, whose code the MK path would grow (small launches slowed by 5-14 % with it compiled in)
+        if (a.multi_key)
+            launch_chunked_x<NR, OPEN, FRAME, 5>(grid, s, b);
+        else
+            launch_chunked_x<NR, OPEN, FRAME, 4>(grid, s, b);
+        if (whole_possible)
+            launch_chunked_x<NR, OPEN, FRAME, 3>(grid, s, b);
+        return;
     }
-    launch_chunked_x<NR, OPEN, FRAME>(ct, grid, s, a);
+    launch_chunked_x<NR, OPEN, FRAME>(grid, s, a);
 }
 
 // Records per chunk of the chunked kernel's dealt-out assignment (BatchArgs::chunk), 0 for contiguous ranges. Each
@@ -1101,10 +1072,8 @@ static void launch_chunked(bool ct, unsigned grid, hipStream_t s, const BatchArg
 #define CHUNKS_PER_WG 8
 #endif
 #define CHUNK_MIN_RECS 256
-#ifndef BALANCE
-#define BALANCE 1  // many-key batches: workgroup ranges balanced by weight (balance_*_kernel)
-#endif
-#define BALANCE_MIN_RECS ((size_t)131072)  // ... from this many records (2 x 256 per workgroup)
+// many-key batches: workgroup ranges balanced by weight (balance_*_kernel) from this many records (2 x 256 per workgroup)
+#define BALANCE_MIN_RECS ((size_t)131072)
 static u64 deal_chunk(u64 nrecs, u64 grid)
 {
     for (u64 k = CHUNKS_PER_WG; k >= 2; k /= 2) {
@@ -1167,7 +1136,7 @@ static int launch_gcm(const KeyEntry *keys, u32 nkeys, int nr, int ncu, int sche
     if (grid < 1)
         grid = 1;
     a.chunk = deal_chunk(nrecs, grid);
-#define CHUNKED_LAUNCH(nr_, op, frame_) launch_chunked<nr_, op, frame_>(ct, (unsigned)grid, s, a)
+#define CHUNKED_LAUNCH(nr_, op, frame_) launch_chunked<nr_, op, frame_>((unsigned)grid, s, a)
 #define CHUNKED_BY_KEY(frame_)                                                                                          \
     do {                                                                                                                \
         if (nr == 10) {                                                                                                 \
@@ -1209,21 +1178,13 @@ static int launch_gcm(const KeyEntry *keys, u32 nkeys, int nr, int ncu, int sche
 // spans of 2^e, their partials at `part` (nspans x 16 B, device-addressable), then the combine launch, which writes the
 // tag or ok[0] and sets done_flag[0] when given.
 template <int NR, bool OPEN>
-static void launch_span_kernel(bool ct, u32 nspans, hipStream_t s, const BatchArgs &a, u32 span, u32 units, void *part)
+static void launch_span_kernel(u32 nspans, hipStream_t s, const BatchArgs &a, u32 span, u32 units, void *part)
 {
-    COUNT_LAUNCH(6);
-#if SEG_COOP  // (one instantiation for both settings, as launch_chunked_x)
-    (void)ct;
+    COUNT_LAUNCH(6);  // (the CT instantiation for every keyset, as launch_chunked_x)
     gcm_span_kernel<NR, OPEN, true><<<nspans, ENGINE_WG, SPAN_LDS, s>>>(a, span, units, (u32x4 *)part);
-#else
-    if (ct)
-        gcm_span_kernel<NR, OPEN, true><<<nspans, ENGINE_WG, SPAN_LDS, s>>>(a, span, units, (u32x4 *)part);
-    else
-        gcm_span_kernel<NR, OPEN, false><<<nspans, ENGINE_WG, SPAN_LDS, s>>>(a, span, units, (u32x4 *)part);
-#endif
 }
 
-static int launch_span(const KeyEntry *key, int nr, bool ct, bool open, const ptls_mi355x_record_t &one, const void *in,
+static int launch_span(const KeyEntry *key, int nr, bool open, const ptls_mi355x_record_t &one, const void *in,
                        const void *aad, void *out, uint8_t *ok, u32 units, u32 e, u32 nspans, void *part, u32 *done_flag,
                        u32 done_token, hipStream_t s)
 {
@@ -1233,14 +1194,14 @@ static int launch_span(const KeyEntry *key, int nr, bool ct, bool open, const pt
     const u32 span = 1u << e;
     if (nr == 10) {
         if (open)
-            launch_span_kernel<10, true>(ct, nspans, s, a, span, units, part);
+            launch_span_kernel<10, true>(nspans, s, a, span, units, part);
         else
-            launch_span_kernel<10, false>(ct, nspans, s, a, span, units, part);
+            launch_span_kernel<10, false>(nspans, s, a, span, units, part);
     } else {
         if (open)
-            launch_span_kernel<14, true>(ct, nspans, s, a, span, units, part);
+            launch_span_kernel<14, true>(nspans, s, a, span, units, part);
         else
-            launch_span_kernel<14, false>(ct, nspans, s, a, span, units, part);
+            launch_span_kernel<14, false>(nspans, s, a, span, units, part);
     }
     HIP_TRY(hipGetLastError());
     const size_t clds = GHASH_TABLE_BYTES + 16 * 257;
@@ -1263,10 +1224,10 @@ static bool spread_eligible(const ptls_mi355x_keyset_t *ks, size_t nrecs, int fr
     return frame == 0 && nrecs >= 2 && nrecs < (size_t)ks->ds->ncu && nrecs <= SPREAD_MAX_RECS && (ks->ct || use_chunked(ks->schedule));
 }
 
-// a batch that may launch the W8 pair (launch_chunked): chunked, W8_MIN_RECS records (TLS 1.2 framing with W8_TLS12)
-static bool w8_eligible(const ptls_mi355x_keyset_t *ks, size_t nrecs, int frame)
+// a batch that may launch the W8 pair (launch_chunked): chunked, W8_MIN_RECS records
+static bool w8_eligible(const ptls_mi355x_keyset_t *ks, size_t nrecs)
 {
-    return W8_HORNER && (frame != 2 || W8_TLS12) && nrecs >= W8_MIN_RECS && (ks->ct || use_chunked(ks->schedule));
+    return nrecs >= W8_MIN_RECS && (ks->ct || use_chunked(ks->schedule));
 }
 
 // orders a launch on `s` that uses the keyset's spread scratch after the last launch that used it;
@@ -1368,12 +1329,8 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
         return -1;
     LAUNCH_CLEAR();  // (the grouping kernels and launch_gcm's launch are checked after this)
     // ungrouped many-key batches: group the records by key on the device first (see key_hist_kernel)
-#ifndef KEY_GROUP_DISABLE
     const bool group = use_chunked(ks->schedule) && ks->nkeys > 1 && ks->nkeys <= KEY_GROUP_MAX_KEYS && nrecs > 1 &&
                        nrecs <= 0xffffffffu;
-#else
-    const bool group = false;
-#endif
     int ret;
     // the keyset's scratch (spread pieces, key grouping) is shared by its launches on every stream: ks->mu is held from
     // taking it through the launch and the use event after it
@@ -1384,7 +1341,7 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
     if (hpl == nullptr && spread_eligible(ks, nrecs, frame)) {
         lk.lock();
         spread = spread_scratch_locked(ks, s, nrecs);
-    } else if (hpl == nullptr && w8_eligible(ks, nrecs, frame)) {  // (a spread launch never takes the W8 pair)
+    } else if (hpl == nullptr && w8_eligible(ks, nrecs)) {  // (a spread launch never takes the W8 pair)
         lk.lock();
         w8flags = w8_flags_locked(ks, s);
     }
@@ -1392,7 +1349,7 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
         if (!lk.owns_lock())
             lk.lock();
         // scratch: ctl[2] | counts[nkeys + 1] | perm[n] | (8-byte aligned) grouped descriptors[n] | balance tiles | bounds
-        const bool balance = BALANCE && nrecs >= BALANCE_MIN_RECS;
+        const bool balance = nrecs >= BALANCE_MIN_RECS;
         const size_t ntiles = (nrecs + BALANCE_TILE - 1) / BALANCE_TILE, ncu = (size_t)ks->ds->ncu;
         const size_t gwords = ((2 + ks->nkeys + 1 + nrecs + 1) & ~(size_t)1) + nrecs * (sizeof(ptls_mi355x_record_t) / 4);
         const size_t twords = balance ? (ntiles + 1) & ~(size_t)1 : 0, bwords = balance ? 2 * (ncu + 1) : 0;
@@ -1604,20 +1561,12 @@ int ptls_mi355x_quiclb_batch(ptls_mi355x_keyset_t *ks, const ptls_mi355x_cid_t *
 
 }  // extern "C"
 
-#ifndef PERREC_FLAG
-#define PERREC_FLAG 1                       // a lone record's launch publishes a completion word the host polls (roundtrip)
-#endif
+// a lone record's launch publishes a completion word the host polls (roundtrip) for this long
 #define PERREC_FLAG_SPIN_US 2000  // + 0.5 us per staged KiB: long records (the span path) poll to their end too
 #ifndef SPAN_MIN_BYTES
 #define SPAN_MIN_BYTES ((size_t)262144)  // a lone record from this length runs over many workgroups (launch_span)
 #endif
 #define PERREC_FLAG_MAX_BYTES ((size_t)1 << 20)  // staged bytes of a call that polls (larger ones wait for the stream)
-#ifndef CT_UNIT_SHIFT
-#define CT_UNIT_SHIFT 0  // per-record launches of a constant-time keyset: unit length x 2^CT_UNIT_SHIFT
-#endif
-#ifndef PERREC_HP_FUSED
-#define PERREC_HP_FUSED 1  // encrypt_s: the header-protection mask computed by the seal launch (BatchArgs::hp)
-#endif
 
 // PTLS_MI355X_COMBINE_STATS=1: per-record launches, calls and the host time of run_calls, printed at exit (tools/gpu_mt.sh)
 static struct CombineStats {
@@ -1806,9 +1755,9 @@ static void run_calls(DeviceState *ds, OneCall *const *c, size_t n)
         if ((1u << span_e) > SPAN_MAX_UNITS)
             span_units = span_e = span_n = 0;
     }
-    // header-protection masks: computed by the chunked seal launch itself (PERREC_HP_FUSED), else by a second launch
-    // (hp_kernel) after the seal, or after the span kernels
-    const bool hp_fused = hp && PERREC_HP_FUSED && span_n == 0 && (c0.ks->ct || use_chunked(c0.ks->schedule));
+    // header-protection masks: computed by the chunked seal launch itself (BatchArgs::hp), else by a second launch
+    // (hp_kernel) after the lockstep seal, or after the span kernels
+    const bool hp_fused = hp && span_n == 0 && (c0.ks->ct || use_chunked(c0.ks->schedule));
     // completion words: one per workgroup of the last kernel (the GCM launch: one workgroup per record up to the CU
     // count; the header-protection launch: aux_grid)
     const size_t nflags = hp && !hp_fused ? (size_t)aux_grid(n, ds->ncu) : (n < (size_t)ds->ncu ? n : (size_t)ds->ncu);
@@ -1860,15 +1809,10 @@ static void run_calls(DeviceState *ds, OneCall *const *c, size_t n)
             // wave ~2 us of latency, a unit combine ~0.15 us); steps / 2^k units balance the two (tools/latency.py).
             // Long records, and batches (one workgroup per record), pass CHUNK_LOG2: the kernel's scan then picks.
             const size_t steps = ((c0.aadlen + 15) / 16 + (c0.len + 15) / 16 + 1 + ENGINE_G - 1) / ENGINE_G;
-            // (the constant-time variant: units CT_UNIT_SHIFT times longer, whose ends cost it 4 GHASH multiplies and
-            // whose combine links a whole gmul_tab each)
-            const u32 ushift = c0.ks->ct ? CT_UNIT_SHIFT : 0u;
-            u32 unit_log2 = n > 1 ? CHUNK_LOG2 : steps <= 24 ? 0 : steps <= 96 ? 1 : steps <= 400 ? 2 : steps <= 1600 ? 3 : CHUNK_LOG2;
-            if (n == 1)
-                unit_log2 = unit_log2 + ushift < CHUNK_LOG2 ? unit_log2 + ushift : CHUNK_LOG2;
+            const u32 unit_log2 = n > 1 ? CHUNK_LOG2 : steps <= 24 ? 0 : steps <= 96 ? 1 : steps <= 400 ? 2 : steps <= 1600 ? 3 : CHUNK_LOG2;
             // (calls staging at most 1 MiB: a larger record's launch runs for hundreds of microseconds or more, which
             // the caller need not spend spinning on a core)
-            const bool flag = PERREC_FLAG && call.mapped() && c0.ks->schedule != PTLS_MI355X_SCHEDULE_LOCKSTEP &&
+            const bool flag = call.mapped() && c0.ks->schedule != PTLS_MI355X_SCHEDULE_LOCKSTEP &&
                               (total <= PERREC_FLAG_MAX_BYTES || span_n != 0);
             // this call's completion token (never 0, and never the value an earlier call left in these words)
             const u32 token = flag ? next_done_token() : 0u;
@@ -1877,7 +1821,7 @@ static void run_calls(DeviceState *ds, OneCall *const *c, size_t n)
             if (ret == 0)
                 ret = call.roundtrip(up, [&] {
                     if (span_n != 0) {
-                        if (launch_span(kbase, nr, c0.ks->ct, open, first, d, d, d, d + off_ok, span_units, span_e, span_n, d + off_span,
+                        if (launch_span(kbase, nr, open, first, d, d, d, d + off_ok, span_units, span_e, span_n, d + off_span,
                                         flag && !hp ? (u32 *)(d + off_flag) : nullptr, token, s) != 0)
                             return -1;
                     } else {

@@ -74,34 +74,17 @@ __device__ __forceinline__ u32 lane_here()
 #define CT_PROBE_CONST 0
 #endif
 
-#ifndef ENGINE_FAST_STEP
-#define ENGINE_FAST_STEP 1         // wave-uniform fast path for steps where every lane holds a full text block
-#endif
-
-#ifndef CT_TREE
-#define CT_TREE 1                  // constant-time mode: the lanes' last powers by a uniform-table tree after the loop
-#endif
-#ifndef CT_COMBINE_TREE
-#define CT_COMBINE_TREE 1          // constant-time mode: a record's unit partials combined by a uniform-table tree
-#endif
-#ifndef SEG_COOP
-#define SEG_COOP 1                 // window-major power tables, the lanes' last powers by coop_last_powers (both modes)
-#endif
-// GHASH table layouts (build_ghash_tables `wmask`: bit t = table t window-major, ghash.h). With SEG_COOP the power
-// tables H^1..H^7 (slots 0..6) and the unit combine power (slot 8, gmul_group_w) in both modes; H^8 (slot 7, the
-// Horner table every lane reads at the same window) stays nibble-major.
-#define GHASH_WMASK(ct) (SEG_COOP ? 0x17Fu : 0u)
-// the constant-time mode's combine tree keeps combine powers in tables 4..6: only without SEG_COOP (H^5..H^7 there)
-#define CT_COMB_TREE_ON (CT_COMBINE_TREE && !SEG_COOP)
+// GHASH table layouts (build_ghash_tables `wmask`: bit t = table t window-major, ghash.h): the power tables H^1..H^7
+// (slots 0..6) and the unit combine power (slot 8, gmul_group_w) window-major; H^8 (slot 7, the Horner table every lane
+// reads at the same window) stays nibble-major. (Late round 3: the lanes' last powers by coop_last_powers in both modes;
+// the per-lane-table and uniform-table-tree segment ends and combine it replaced are no longer in the source.)
+#define GHASH_WMASK 0x17Fu
 
 #ifndef ALIGN_MIN_STEPS
 #define ALIGN_MIN_STEPS 64         // whole records of this many steps may take one more step to align their stores
 #endif
 
-#define ENGINE_G 8                 // lanes per record
-#ifndef ENGINE_NB
-#define ENGINE_NB 1                // AES-CTR blocks per lane per step (independent chains in flight)
-#endif
+#define ENGINE_G 8                 // lanes per record (each runs one AES-CTR block per step: the counter cache's form)
 #ifndef ENGINE_WG
 #define ENGINE_WG 1024             // threads per workgroup (one workgroup per CU)
 #endif
@@ -155,16 +138,11 @@ __device__ __forceinline__ u32 lane_here()
 // (window-major for EXT 4, nibble-major for EXT 3), the unit partials of at most W8_RUN_UNITS units at CLDS_PART
 // (their first 2 KiB the groups' E(K, J0) slots in whole runs; the table build's scratch before a run), at W8_TAB_COMB
 // the unit combine power (window-major, EXT 4) or H^2 (nibble-major, EXT 3)
-#ifndef W8_HORNER
-#define W8_HORNER 1  // (round 4: on; profiles/r4/w8_ab.txt, w8all_ab.txt)
-#endif
+// (round 4: profiles/r4/w8_ab.txt, w8all_ab.txt.) TLS 1.2-framed batches take them too, although EXT 4's TLS 1.2 seal
+// spills 96 B per lane: 131072 x 16 KiB records 1036.9 -> 1172.1 GiB/s seal+open, 1M x 1200 B 907.2 -> 979.1
+// (tools/ab_tls12.py, profiles/r4/tls12_w8_ab.txt)
 #ifndef W8_MIN_STEPS
 #define W8_MIN_STEPS 64
-#endif
-#ifndef W8_TLS12
-// TLS 1.2-framed batches in the W8 kernels too, although EXT 4's TLS 1.2 seal spills 96 B per lane: 131072 x 16 KiB
-// records 1036.9 -> 1172.1 GiB/s seal+open, 1M x 1200 B 907.2 -> 979.1 (tools/ab_tls12.py, profiles/r4/tls12_w8_ab.txt)
-#define W8_TLS12 1
 #endif
 #ifndef W8_MIN_RECS
 // batches of fewer records keep the 4-bit kernel. Round 4 set 2048 (256 x 16 KiB -5 %, 1000 x 1200 B -4 %, 1000 x 16 KiB
@@ -173,54 +151,14 @@ __device__ __forceinline__ u32 lane_here()
 // ±0.3 % with 64), profiles/r5/w8_min_recs_ab.txt
 #define W8_MIN_RECS 256
 #endif
-#ifndef W8_SWAP
 // (round 5) the W8 kernels' LDS map puts the 8-bit H^8 table at [0, 64K) and the AES T-tables at [64K, 128K): the
 // table's address bytes are then two (window, value), formed by one v_perm from registers that stay fixed through the
 // loop, and the AES addresses take their 64 KiB slot from laneoff's byte 2 in the same v_perm (aes_tt.h TE_ADDR)
-#define W8_SWAP 1
-#endif
-// (round 5) whole runs of the W8 serial kernel (EXT 4: uniform records under W8_MIN_STEPS steps) in 4-lane groups
-// (ghash.h, gcm_chunked_kernel): quic1200 +3.3-3.9 % (profiles/r5/g4_ab.txt); 0 keeps 8-lane groups
-#ifndef W8_G4
-#define W8_G4 1
-#endif
-// (round 5) gmul8's selects by bit 3 of the lane from a constant lane mask (ghash.h)
-// (round 5) steps without a text or length position skip the AES (segment.h)
-#ifndef SKIP_EMPTY_AES
-#define SKIP_EMPTY_AES 1
-#endif
-#ifndef GMUL8_CONST_MASK
-#define GMUL8_CONST_MASK 1
-#endif
-#define GMUL8_LANE() (GMUL8_CONST_MASK && W8_SWAP ? 0u : lane_here())  // (lane_here is a volatile asm: not evaluated unless needed)
-// ... and its cut runs too (the units keep their 8-lane-step bounds and combine power; gcm_chunked_kernel): measured
-// -6 % on mixed (units twice as long in time, so the run tails wait twice as long; also with each run cut into at least
-// 128 units), -18 % with units of half the length (twice the partials and combine links): off (profiles/r5/g4_ab.txt)
-#ifndef W8_G4_CUT
-#define W8_G4_CUT 0
-#endif
-// (round 5) the W8 kernels' unframed steps outside the steady range as one pass with the non-text inputs loaded ahead of
-// the AES (segment.h): measured within +-0.5 % of the per-case setup_step / finish_step on quic1200 and mixed
-// (profiles/r5/g4_ab.txt): off
-#ifndef W8_LEAN_STEP
-#define W8_LEAN_STEP 0
-#endif
-// (round 5) 4-lane groups store a line's two 64-byte halves together: a lane holds the first half's block one steady
-// step and stores it beside the second (segment.h). Half lines stored a step apart leave the L2 as two write-backs of
-// the line (tools/mb/wcal.hip: 1.07-1.08x the bytes; paired, 1.00x)
-#ifndef G4_PAIR_STORES
-#define G4_PAIR_STORES 1
-#endif
-// (round 6) a 4-lane group's open aligns its steps to the record's text, not to its output (segment.h): text block 0
-// starts a step, so the AAD step needs no keystream, as in the seal (1200-byte open: 19 AES steps instead of 20)
-#ifndef G4_OPEN_TEXT_STEPS
-#define G4_OPEN_TEXT_STEPS 1
-#endif
-// ... and its steady steps, no longer aligned to the output's lines, still store every 128-byte line in one step: a lane
-// holds up to two blocks (the line's halves) until the step that produces the line's last block (segment.h)
-#ifndef G4_LINE_HOLD
-#define G4_LINE_HOLD 1
-#endif
+#define W8_H8_BASE 0u                    // the W8 kernels' 8-bit H^8 table
+#define W8_AES_BASE (u32)LDS_AES_BYTES   // ... and their AES T-tables
+// (round 5) whole runs of the W8 serial kernel (EXT 4: uniform records under W8_MIN_STEPS steps) run in 4-lane groups
+// (ghash.h, gcm_chunked_kernel): quic1200 +3.3-3.9 % (profiles/r5/g4_ab.txt); its cut runs keep 8-lane groups (in 4-lane
+// groups mixed measured -6 %: units twice as long in time, so the run tails wait twice as long)
 // (round 6) the serial W8 kernels' waves issue by the steps left in their segment (s_setprio 3..0 in bands of this many
 // steps, segment.h): the waves of a SIMD then end equal claims together instead of in the order of their age, which
 // left a run's last wave alone on its SIMD. tls64k +4.3 %, quic64k +5.0 %, mixed +0.7 %, quic1200 +0.4 %; the tree
@@ -230,22 +168,15 @@ __device__ __forceinline__ u32 lane_here()
 #endif
 // ... and the tree kernel's (EXT 3, long whole records) in bands of TREE_PRIO_BAND steps: 32 gave tls16k +0.4 / +0.7 %,
 // AES-256 16 KiB +0.6 %, 256K x 16 KiB +2.2 % on two boxes, 16 a further +0.25 to +0.8 % on tls16k (bands of 4
-// measured -2.3 %, of 64 -2 to -3 %; the waves nearest their segment's end first, TREE_PRIO_INV, -1 to -2 %)
+// measured -2.3 %, of 64 -2 to -3 %; the waves nearest their segment's end first -1 to -2 %)
 // (profiles/r6/tree_prio_ab.txt, tree_prio_band_ab.txt); 0: the tree kernel keeps its issue order
 #ifndef TREE_PRIO_BAND
 #define TREE_PRIO_BAND 16
 #endif
-#ifndef TREE_PRIO_INV
-#define TREE_PRIO_INV 0
-#endif
-// ... and 8-lane groups whose steps straddle lines (cut runs' units) store each line in one step (segment.h)
-#ifndef G8_PAIR_STORES
-#define G8_PAIR_STORES 1
-#endif
 // a W8 pair's flag block per workgroup (BatchArgs::w8_flags): [0] the runs EXT 4 left to EXT 3 (W8_SKIP_LIST + 1:
 // more than the list holds, or records past 2^32), then per listed run (walk order) its first record and the end of
 // the chunk that holds it
-// (round 6) multi-key runs (MK runs, EXT 4): a many-key batch's connections of short uniform records (under
+// (round 6) multi-key runs (MK runs, EXT 5): a many-key batch's connections of short uniform records (under
 // W8_MIN_STEPS 8-lane steps, fewer than WHOLE_MIN_RECS records each: QUIC packets of many connections) share one
 // whole-record run of up to MK_SLOTS connections and CRUN_RECS records, in 4-lane groups, each connection's 4-bit H^4 and
 // H tables in a 16 KiB slot of [0, 64K) (ghash.h gmul4w). A connection's records are taken 16 at a time (a wave's
@@ -258,12 +189,6 @@ __device__ __forceinline__ u32 lane_here()
 #ifndef MK_MIN_FIRST
 #define MK_MIN_FIRST 3
 #endif
-#ifndef MK_RUNS
-#define MK_RUNS 1
-#endif
-#ifndef MK_EARLY_SCAN
-#define MK_EARLY_SCAN 1
-#endif
 #define MK_SLOTS 4
 #define MK_NONE 0xffffffffu
 #define MK_SLOT_BYTES 16384
@@ -272,8 +197,6 @@ __host__ __device__ constexpr u32 mk_htab(u32 kslot) { return ((kslot & 0xc0u) <
 
 #define W8_FLAG_WORDS 32
 #define W8_SKIP_LIST ((W8_FLAG_WORDS - 1) / 2)
-#define W8_H8_BASE (W8_SWAP ? 0u : (u32)LDS_AES_BYTES)   // the W8 kernels' 8-bit H^8 table
-#define W8_AES_BASE (W8_SWAP ? (u32)LDS_AES_BYTES : 0u)  // ... and their AES T-tables
 #define W8_RUN_UNITS 512  // units per run of a launch pair (both kernels: their runs must be the same)
 #define W8_TAB_H (LDS_AES_BYTES + 8 * GHASH_TABLE_BYTES)
 #define W8_TAB_COMB (CLDS_PART + 16 * W8_RUN_UNITS)

@@ -16,7 +16,7 @@ __device__ __forceinline__ u32 unit_mul(u32 steps, u32 log2, u32 cap)
 // of a pair identically, since each skips exactly the other's runs
 __device__ __forceinline__ u32 run_unit_cap(const BatchArgs &args)
 {
-    return W8_HORNER && args.w8_split ? (u32)W8_RUN_UNITS : (u32)CRUN_UNITS;
+    return args.w8_split ? (u32)W8_RUN_UNITS : (u32)CRUN_UNITS;
 }
 
 // Descriptors whose len exceeds PTLS_MI355X_MAX_RECORD_LEN, whose AAD exceeds PTLS_MI355X_MAX_AAD_LEN or whose key_idx
@@ -41,7 +41,7 @@ __device__ __forceinline__ bool spread_long(const BatchArgs &a, const ptls_mi355
 }
 
 // Seals / opens one whole record per G-lane group.
-template <int NR, bool OPEN, int NB>
+template <int NR, bool OPEN>
 __device__ __forceinline__ void process_group(const BatchArgs &args, const lds_u8 *lds, const u32 (&rk)[NR + 1][4], u32 iv0,
                                               u32 iv1, u32 iv2, u64 rec, bool valid, u32 j, u32 laneoff, u32 tsel_horner)
 {
@@ -56,8 +56,8 @@ __device__ __forceinline__ void process_group(const BatchArgs &args, const lds_u
     const u32 K = valid ? gcm_steps<OPEN, 0>(r) : 0;
     u32x4 acc;
     u32 okw;
-    gcm_segment<NR, OPEN, NB>(args, lds, rk, iv0, iv1, iv2, r, valid, 0, K, j, laneoff, tsel_horner, acc, true, okw,
-                              true, LDS_EKSLOT + 16u * (threadIdx.x / ENGINE_G));
+    gcm_segment<NR, OPEN>(args, lds, rk, iv0, iv1, iv2, r, valid, 0, K, j, laneoff, tsel_horner, acc, true, okw, true,
+                          LDS_EKSLOT + 16u * (threadIdx.x / ENGINE_G));
     if (OPEN && okw <= 1)
         args.ok[rec] = (uint8_t)okw;
 }
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         }
         if (key_idx != loaded_key) {
             __syncthreads();  // no wave still reads the previous key's tables
-            build_ghash_tables(lds, args.keys + key_idx, ENGINE_G, 8, 0, 0, 0, false, GHASH_WMASK(false));
+            build_ghash_tables(lds, args.keys + key_idx, ENGINE_G, 8, 0, 0, 0, GHASH_WMASK);
             __syncthreads();
             loaded_key = key_idx;
         }
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         const u64 ngroups = (run_end - pos + RPW - 1) / RPW;
         for (u64 grp = wave; grp < ngroups; grp += waves_per_wg) {
             const u64 rec = pos + grp * RPW + slot;
-            process_group<NR, OPEN, ENGINE_NB>(args, lds, rk, iv0, iv1, iv2, rec, rec < run_end, j, laneoff, tsel_horner);
+            process_group<NR, OPEN>(args, lds, rk, iv0, iv1, iv2, rec, rec < run_end, j, laneoff, tsel_horner);
         }
         pos = run_end;
     }
@@ -147,9 +147,6 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
 #ifndef ENGINE_HOOKS
 #define ENGINE_HOOKS 1
 #endif
-#ifndef COMBINE_SCATTER
-#define COMBINE_SCATTER 1  // round 5: a record's unit combine as a scattered chain of group products (ghash.h)
-#endif
 #define EXT_RUN_ROWS 256
 __device__ unsigned long long g_ext_runs[EXT_RUN_ROWS][8];
 
@@ -158,12 +155,6 @@ __device__ unsigned long long g_ext_runs[EXT_RUN_ROWS][8];
 #endif
 #ifndef RUN_MAX_CHAIN
 #define RUN_MAX_CHAIN 36  // longest unit-combine chain a cut run's unit length may give a record (run_unit_log2)
-#endif
-#ifndef EARLY_GHASH
-#define EARLY_GHASH 1
-#endif
-#ifndef MEAS_BUILD_ONCE
-#define MEAS_BUILD_ONCE 0
 #endif
 #define EARLY_GHASH_WAVE 11  // waves 11..15 (320 threads: one per table window of 9 tables) build a one-key launch's tables
 
@@ -216,9 +207,9 @@ static_assert(RUN_DONE_OFF + (MK_SLOTS - 1) * (int)(sizeof(KeyEntry) / 4) <= RUN
 static_assert(MK_SLOTS * ((WHOLE_MIN_RECS + 15) / 16) <= CRUN_RECS + 16 && MK_SLOTS * MK_SLOT_BYTES <= 65536,
               "MK claims in the ubase words, slots in [0, 64K)");
 
-// (round 6) scan_mk (EXT 4, many-key batches; called by scan_run once it has found that the run at p is the short
+// (round 6) scan_mk (EXT 5, many-key batches; called by scan_run once it has found that the run at p is the short
 // uniform records of one connection with fewer records than the workgroup has 8-lane groups, which it would otherwise
-// cut into units): joins that connection and the next ones into one multi-key whole run (common.h MK_RUNS) while each
+// cut into units): joins that connection and the next ones into one multi-key whole run (common.h, MK runs) while each
 // is complete within the scan window (CRUN_RECS records; its last record followed by another key or the range end), has
 // fewer than WHOLE_MIN_RECS records, all of them accepted descriptors of a valid key, and all the run's records stay
 // within UNIFORM_SLACK steps of each other and under W8_MIN_STEPS steps -- so a W8 pair's EXT 3 kernel, which scans
@@ -339,7 +330,7 @@ __device__ __forceinline__ void scan_run(const BatchArgs &args, const ptls_mi355
         ((lds_u32 *)(rs + RUN_KEY_OFF))[lane] = ((const u32 *)(args.keys + key))[lane],
         ((lds_u32 *)(rs + RUN_KEY_OFF))[lane + 64] = ((const u32 *)(args.keys + key))[lane + 64];
     u32 steps[Q], nc[Q], bkt[Q];
-    constexpr bool MKS = MK_RUNS && EXT == 5;
+    constexpr bool MKS = EXT == 5;
     u32 mkk[MKS ? Q : 1], mks[MKS ? Q : 1];  // (MK: each record's key, and its steps if scan_mk may take it, else ~0)
     // (MK: the key of the record after a full window, so that a connection ending exactly there counts as complete)
     const u32 mk_after = MKS && args.multi_key && lim == (u32)CRUN_RECS && p + lim < end ? recs[p + lim].key_idx : 0xffffffffu;
@@ -389,7 +380,7 @@ __device__ __forceinline__ void scan_run(const BatchArgs &args, const ptls_mi355
             smin = min(smin, steps[q]), smax = max(smax, steps[q]);
     smin = wave_min(smin);
     smax = wave_max(smax);
-    if constexpr (MK_RUNS && EXT == 5) {
+    if constexpr (MKS) {
         // (round 6) a connection of short uniform records, fewer than the workgroup's groups: join the next
         // connections into one multi-key whole run (scan_mk) instead of cutting it into units
         if (args.multi_key && key < args.nkeys && n >= (u32)MK_MIN_FIRST && n < (u32)WHOLE_MIN_RECS && smax < (u32)W8_MIN_STEPS &&
@@ -511,7 +502,7 @@ __device__ __forceinline__ void scan_run(const BatchArgs &args, const ptls_mi355
         rs[RC_CLAIM] = 0;
         rs[RC_LOG2] = log2;
         rs[RC_HPNEXT] = 0;
-        if constexpr (MK_RUNS && EXT == 5)  // (only the MK kernel reads it)
+        if constexpr (MKS)  // (only the MK kernel reads it)
             rs[RC_MK] = 0;
     }
 }
@@ -705,7 +696,7 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
     u32 loaded_key = args.multi_key ? args.recs[piece_record(w)].key_idx : 0u;
     if (wave >= EARLY_GHASH_WAVE)
         build_ghash_tables(lds, args.keys + loaded_key, 9, src8, 0, EARLY_GHASH_WAVE * 64, ENGINE_WG - EARLY_GHASH_WAVE * 64,
-                           false, GHASH_WMASK(CT));
+                           GHASH_WMASK);
     else
         build_aes_tables(lds, 0, EARLY_GHASH_WAVE * 64);
     __syncthreads();
@@ -716,7 +707,7 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
         const ptls_mi355x_record_t r = args.recs[t];
         const u32 kidx = args.multi_key ? __builtin_amdgcn_readfirstlane(r.key_idx) : 0u;  // (< nkeys: spread_long)
         if (kidx != loaded_key) {
-            build_ghash_tables(lds, args.keys + kidx, 9, src8, 0, 0, 0, false, GHASH_WMASK(CT));  // (freed by the last barrier)
+            build_ghash_tables(lds, args.keys + kidx, 9, src8, 0, 0, 0, GHASH_WMASK);  // (freed by the last barrier)
             __syncthreads();
             loaded_key = kidx;
         }
@@ -742,8 +733,8 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
             }
             u32x4 acc;
             u32 okw;
-            gcm_segment<NR, OPEN, 1, 0, CT>(args, lds, rk, iv0, iv1, iv2, r, valid, m_lo, m_hi, j, laneoff, tsel_horner, acc,
-                                            false, okw, false, CLDS_PART + 16u * uu);
+            gcm_segment<NR, OPEN, 0, CT>(args, lds, rk, iv0, iv1, iv2, r, valid, m_lo, m_hi, j, laneoff, tsel_horner, acc, false,
+                                         okw, false, CLDS_PART + 16u * uu);
             if (valid && j == G - 1)  // (the record's last unit includes E(K, J0), gcm_segment)
                 s_part[uu] = acc;
         }
@@ -758,14 +749,14 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
         if (split) {
             if (wave == 1)
                 build_elem_table(lds, tsel_ml, u32x4{key->h[key_pow2_idx(mL)][0], key->h[key_pow2_idx(mL)][1],
-                                                     key->h[key_pow2_idx(mL)][2], key->h[key_pow2_idx(mL)][3]}, 64, SEG_COOP);
+                                                     key->h[key_pow2_idx(mL)][2], key->h[key_pow2_idx(mL)][3]}, 64, true);
             if (wave == 0) {
                 const u32 lane = lane_here(), c = lane / G, L = 1u << (e - 3), ulo = c * L, uhi = min(ulo + L, nu);
                 u32x4 g = {0, 0, 0, 0};
                 if (ulo < uhi) {
                     g = s_part[uhi - 1];
                     for (u32 i = uhi - 1; i-- > ulo;)
-                        g = gmul_combine<CT>(lds, g, tsel_chunk, lane) ^ s_part[i];
+                        g = gmul_combine(lds, g, tsel_chunk, lane) ^ s_part[i];
                 }
                 if (lane % G == 0)
                     s_sum[c] = g;
@@ -778,11 +769,11 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
             if (split) {
                 g = s_sum[7];
                 for (u32 c = 7; c-- > 0;)
-                    g = gmul_combine<CT>(lds, g, tsel_ml, lane) ^ s_sum[c];
+                    g = gmul_combine(lds, g, tsel_ml, lane) ^ s_sum[c];
             } else {
                 g = s_part[nu - 1];
                 for (u32 i = nu - 1; i-- > 0;)
-                    g = gmul_combine<CT>(lds, g, tsel_chunk, lane) ^ s_part[i];
+                    g = gmul_combine(lds, g, tsel_chunk, lane) ^ s_part[i];
             }
             if (lane == 0) {
                 args.spread_part[pbase + s] = g;
@@ -835,38 +826,7 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
 // EXT (FRAME 0 only): 0 = plain; 1 = a spread launch (a small one-key batch, spread_pieces); 2 = seal with
 // header-protection masks (seal_batch_hp). Separate instantiations: the calls these add (spread_pieces, hp_masks_pass)
 // cost the plain kernels' loops registers (16 KiB seal -1.2 % with both compiled into one kernel).
-// Constant-time combine of a record's unc unit partials p[0..unc) (GHASH = sum_i p_i M^(unc-1-i), M the unit power in
-// table 8) by the G lanes of one group: blocks of 8 partials from the front (the first one short, right-aligned on the
-// lanes), each summed by a butterfly in which level k pairs lane l (bit k clear) with lane l + k as v_l M^k + v_(l+k)
-// (tables 8, 4, 5: M, M^2, M^4; every lane the same table), the blocks joined by Horner with M^8 (table 6). ceil(log2
-// unc) products instead of unc - 1 chained ones for unc <= 8. Lane G - 1 holds the result.
-__device__ __noinline__ u32x4 ct_combine_tree(const lds_u8 *lds, const lds_u32x4 *p, u32 unc, u32 j)
-{
-    const u32 nblk = (unc + 7) >> 3, c0 = unc - 8 * (nblk - 1);
-    u32x4 g = {0, 0, 0, 0};
-    for (u32 b = 0; b < nblk; ++b) {
-        const int i = (int)j - 8 + (int)c0 + 8 * (int)b;
-        u32x4 v = i >= 0 ? u32x4(p[i]) : u32x4{0, 0, 0, 0};
-        const u32 lv = b != 0 || c0 > 4 ? 3u : c0 > 2 ? 2u : c0 > 1 ? 1u : 0u;
-        for (u32 l = 0; l < lv; ++l) {
-            const u32 k = 1u << l;
-            const u32x4 y = gmul_tab(lds, v, 0x10000u + (l == 0 ? 8u : 3u + l) * GHASH_TABLE_BYTES);
-            const bool hi = (j & k) != 0;
-            const u32x4 send = hi ? v : y;
-            u32x4 recv;
-            // partner lane l ^ k: quad_perm [1,0,3,2], [2,3,0,1]; for k = 4 row_half_mirror (lane 7 - l), which holds
-            // the same value as lane l ^ 4 once levels 1 and 2 made each quad uniform
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                recv[c] = k == 1   ? (u32)__builtin_amdgcn_update_dpp(0, (int)send[c], 0xB1, 0xF, 0xF, false)
-                          : k == 2 ? (u32)__builtin_amdgcn_update_dpp(0, (int)send[c], 0x4E, 0xF, 0xF, false)
-                                   : (u32)__builtin_amdgcn_update_dpp(0, (int)send[c], 0x141, 0xF, 0xF, false);
-            v = hi ? (recv ^ v) : (y ^ recv);
-        }
-        g = b == 0 ? v : (gmul_tab(lds, g, 0x10000u + 6u * GHASH_TABLE_BYTES) ^ v);
-    }
-    return g;
-}
+// CT is instantiated true only: every LDS access is conflict-free by construction or uniform.
 
 // The W8 tables of the run's key (staged in LDS), by three waves at once: H^8's 4-bit nibble-major table into the
 // partial region (free between runs) as the source of its 8-bit table over slots 0..7, H window-major into slot 8, and
@@ -910,8 +870,8 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
     // (the lane index and what derives from it are computed in the unit loop, lane_here())
     const u32 wave = threadIdx.x >> 6;
     const u32 tsel_horner = 0x10000u + (u32)(G - 1) * GHASH_TABLE_BYTES;
-    constexpr bool W8K = W8_HORNER && (EXT == 3 || EXT == 4 || EXT == 5);  // a W8 kernel (launch_chunked)
-    constexpr bool W8TREE = W8_HORNER && EXT == 3;                  // ... with the butterfly segment end
+    constexpr bool W8K = EXT == 3 || EXT == 4 || EXT == 5;  // a W8 kernel (launch_chunked)
+    constexpr bool W8TREE = EXT == 3;                       // ... with the butterfly segment end
     // the unit combine table: slot 8, or in the W8 kernel's map W8_TAB_COMB
     const u32 tsel_chunk = W8K ? (u32)W8_TAB_COMB : 0x10000u + 8u * GHASH_TABLE_BYTES;
 
@@ -994,12 +954,12 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
     // the AES tables. A one-key launch knows its key before the scan: waves EARLY_GHASH_WAVE.. build its GHASH tables
     // H^1..H^8 meanwhile (and the unit combine table when the launch fixes the unit length: the per-record path),
     // instead of after the prologue barrier; the AES copy keeps the waves in between.
-    const bool early = EARLY_GHASH && !args.multi_key && !W8K;
+    const bool early = !args.multi_key && !W8K;
     const u32 fixed_usrc = args.unit_log2 == CHUNK_LOG2 ? 8u : args.unit_log2 == 0 ? 7u : 8u + args.unit_log2;
     const bool early_combine = early && args.unit_log2 < CHUNK_LOG2;
     if (early && wave >= EARLY_GHASH_WAVE) {
         build_ghash_tables(lds, args.keys, early_combine ? 9u : 8u, fixed_usrc, 0, EARLY_GHASH_WAVE * 64,
-                           ENGINE_WG - EARLY_GHASH_WAVE * 64, CT && CT_COMB_TREE_ON, GHASH_WMASK(CT));
+                           ENGINE_WG - EARLY_GHASH_WAVE * 64, GHASH_WMASK);
     } else if (wave == 0) {
         if (beg < end)
             scan_run<OPEN, FRAME, true, EXT>(args, recs, beg, end, (lds_u32 *)(lds + CLDS_RUN0));
@@ -1032,8 +992,8 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         const bool whole_run = __builtin_amdgcn_readfirstlane(rs[RC_WHOLE]);
         const u32 total_units = __builtin_amdgcn_readfirstlane(rs[RC_UNITS]);
         const u32 nhuge = __builtin_amdgcn_readfirstlane(rs[RC_HUGE]);
-        // (round 6) a multi-key run (EXT 4, scan_mk): its connections, 0 for any other run
-        const u32 mk_n = MK_RUNS && EXT == 5 ? __builtin_amdgcn_readfirstlane(rs[RC_MK]) : 0u;
+        // (round 6) a multi-key run (EXT 5, scan_mk): its connections, 0 for any other run
+        const u32 mk_n = EXT == 5 ? __builtin_amdgcn_readfirstlane(rs[RC_MK]) : 0u;
         // the run's unit length in steps (a power of two <= CHUNK_STEPS) and the key element of its combine power
         // H^(G * ustep): [7] = H^8, [9..12] = H^16..H^128, [8] = H^CHUNK_BLOCKS
         const u32 ulog2 = __builtin_amdgcn_readfirstlane(rs[RC_LOG2]), ustep = 1u << ulog2;
@@ -1109,11 +1069,11 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         constexpr bool w8run = W8K;
         // W8 segment ends: the serial chain (1), the tree (2), or a whole run of the serial kernel in 4-lane groups (3:
         // Horner with H^4)
-        const bool g4run = W8K && !W8TREE && (whole ? W8_G4 : W8_G4_CUT);
+        // (cut runs keep 8-lane groups: in 4-lane groups mixed measured -6 %, -18 % with units of half the length,
+        // profiles/r5/g4_ab.txt)
+        const bool g4run = W8K && !W8TREE && whole;
         const u32 w8mode = !w8run ? 0u : W8TREE ? 2u : g4run ? 3u : 1u;
-        // (MEAS_BUILD_ONCE, measurement builds only: a workgroup's later runs keep its first run's tables -- wrong tags
-        // for other keys -- to price the per-run build, profiles/r5/table_build_cost.txt)
-        const bool key_new = key_idx != loaded_key && !(MEAS_BUILD_ONCE && loaded_key != 0xffffffffu);
+        const bool key_new = key_idx != loaded_key;
         if (mk_n != 0) {
             // (round 6) an MK run: each connection's H^4 and H as 4-bit window-major tables in its slot (ghash.h),
             // 128 threads a table; the next other run rebuilds its own tables (loaded_key none)
@@ -1143,11 +1103,8 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             __syncthreads();
             loaded_usrc = usrc;
         } else if (!w8run && (key_idx != loaded_key || loaded_w8 || (!whole && usrc != loaded_usrc))) {
-            // H^1..H^8 and the unit combine power (only the latter when just the unit length changed; constant-time
-            // mode: its powers in tables 4..6 too)
-            constexpr bool CTT = CT && CT_COMB_TREE_ON;
-            build_ghash_tables(lds, key, 9, usrc, key_idx != loaded_key || loaded_w8 ? 0u : CTT ? 4u : 8u, 0, 0, CTT,
-                               GHASH_WMASK(CT));
+            // H^1..H^8 and the unit combine power (only the latter when just the unit length changed)
+            build_ghash_tables(lds, key, 9, usrc, key_idx != loaded_key || loaded_w8 ? 0u : 8u, 0, 0, GHASH_WMASK);
             __syncthreads();
             loaded_key = key_idx;
             loaded_usrc = usrc;
@@ -1158,9 +1115,8 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
 #if ENGINE_PROFILE
         unsigned long long t2 = stamp();
 #endif
-        if (MK_RUNS && EXT == 5 && mk_n != 0) {
+        if (EXT == 5 && mk_n != 0) {
             ++mk_here;  // (ptls_mi355x_debug_counters: MK runs)
-#if MK_EARLY_SCAN
             // the workgroup's last wave scans the next run before it claims: the scan's memory round trips then wait
             // while the other waves work, instead of after the claims, when all of them would wait for it
             if (wave == ENGINE_WG / 64 - 1) {
@@ -1175,7 +1131,6 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                     PROF_ADD(15, stamp() - ts0);
 #endif
             }
-#endif
             {
                 // (round 6) an MK run: each wave claims one of the run's claims (up to 16 records of one connection,
                 // scan_mk) and runs them as a whole run's 4-lane groups do, with the connection's round keys and IV in
@@ -1213,7 +1168,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                         if (!live)
                             r.len = 0, r.aad_len = 0, r.flags = 0;
                         const u32 ekslot = CLDS_PART + 16u * (threadIdx.x / G4);
-                        gcm_segment<NR, OPEN, 1, FRAME, CT, true, (int)G4, true>(
+                        gcm_segment<NR, OPEN, FRAME, CT, true, (int)G4, true>(
                             args, lds, rkm, mv0, mv1, mv2, r, live, 0u, live ? 2u * gcm_steps<OPEN, FRAME>(r) : 0u, j, laneoff, 0u, acc,
                             true, okw, true, ekslot, false, mk_kslot(slot));
                     }
@@ -1271,13 +1226,12 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             }
         };
         bool g4done = false;
-        if constexpr (W8K && !W8TREE && (W8_G4 || W8_G4_CUT)) {
+        if constexpr (W8K && !W8TREE) {
             if (g4run) {
-                // (round 5) the serial W8 kernel's whole runs (and with W8_G4_CUT its cut runs): 16 units a wave in
-                // 4-lane groups (ghash.h). A whole run gives each group a record on 64-byte aligned steps; a cut run's
-                // units keep their 8-lane-step bounds (the stream padded to a multiple of 8 positions, unit k of a
-                // record ending 128 * k positions before its end), each taken in twice as many 4-lane steps, so the
-                // partials, their slots and the combine power are the 8-lane kernel's
+                // (round 5) the serial W8 kernel's whole runs: 16 records a wave in 4-lane groups (ghash.h), each group a
+                // record on 64-byte aligned steps. (g4run implies whole, but the compiler does not see it: the unit
+                // bounds below for !whole never run, and taking them out changes the EXT 4 and 5 kernels' code, so they
+                // wait for the change that next touches this loop)
                 constexpr u32 G4 = 4, RPW4 = 64 / G4;
                 ++g4_here;  // (ptls_mi355x_debug_counters: runs in 4-lane groups)
                 for (;;) {
@@ -1315,9 +1269,9 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                         if (!live)
                             m_lo = m_hi = 0;
                         const u32 ekslot = CLDS_PART + 16u * (whole ? threadIdx.x / G4 : first + unc - 1);
-                        gcm_segment<NR, OPEN, 1, FRAME, CT, true, (int)G4>(args, lds, rk, iv0, iv1, iv2, r, live, 2u * m_lo,
-                                                                         2u * m_hi, j, laneoff, tsel_horner, acc,
-                                                                         unc == 1, okw, whole, ekslot, false);
+                        gcm_segment<NR, OPEN, FRAME, CT, true, (int)G4>(args, lds, rk, iv0, iv1, iv2, r, live, 2u * m_lo, 2u * m_hi,
+                                                                      j, laneoff, tsel_horner, acc, unc == 1, okw, whole,
+                                                                      ekslot, false);
                     }
                     asm volatile("" ::: "memory");
                     const u32 lane = lane_here(), j = lane % G4, u = ub + lane / G4;
@@ -1327,45 +1281,6 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                     unit_of(u, lo, first, unc, k_back);
                     if (OPEN && okw <= 1)  // a whole record's tag check (its length lane)
                         args.ok[ok_at(pos + lo)] = (uint8_t)okw;
-                    if constexpr (W8_G4_CUT) {
-                        if (unc > 1) {  // uniform over the group; a rejected descriptor is always one unit
-                            u32 last = 0;
-                            if (j == G4 - 1) {
-                                s_part[first + unc - 1 - k_back] = acc;
-                                __threadfence_block();  // the partial lands before the count that publishes it
-                                last = atomicAdd((u32 *)&s_done[lo], 1u) == unc - 1;
-                            }
-                            last = (u32)__builtin_amdgcn_update_dpp(0, (int)last, 0xFF, 0xF, 0xF, false);  // quad lane 3
-                            if (last) {
-                                // the record's GHASH: Horner over its partials with the unit power (W8_TAB_COMB), a
-                                // scattered chain over the quad (lane j carries dword j)
-                                const ptls_mi355x_record_t r = recs[pos + lo];
-                                const u32 mul = unit_mul(gcm_steps<OPEN, FRAME>(r), ulog2, run_unit_cap(args));
-                                const Group4Ws k = group4_ws(tsel_chunk, lane);
-                                const u32x4 z = {0, 0, 0, 0};
-                                u32 gs = ((const lds_u32 *)(s_part + first))[j];
-                                for (u32 i = 1; i < unc; ++i) {
-                                    for (u32 t = 0; t < mul; ++t)  // (mul > 1: huge records only)
-                                        gs = group4_scatter(group4_ws_terms(gs, k, z), lane);
-                                    gs ^= ((const lds_u32 *)(s_part + first + i))[j];
-                                }
-                                const u32x4 tag = {(u32)__builtin_amdgcn_update_dpp(0, (int)gs, 0x00, 0xF, 0xF, false),
-                                                   (u32)__builtin_amdgcn_update_dpp(0, (int)gs, 0x55, 0xF, 0xF, false),
-                                                   (u32)__builtin_amdgcn_update_dpp(0, (int)gs, 0xAA, 0xF, 0xF, false),
-                                                   (u32)__builtin_amdgcn_update_dpp(0, (int)gs, 0xFF, 0xF, 0xF, false)};
-                                if (j != G4 - 1) {
-                                } else if (OPEN) {
-                                    const u32x4 rt = *(const u32x4_u *)(args.in + r.in_off + frame_in_skip<OPEN, FRAME>() +
-                                                                        gcm_text_len<OPEN, FRAME>(r));
-                                    const u32x4 d = rt ^ tag;
-                                    args.ok[ok_at(pos + lo)] = (d[0] | d[1] | d[2] | d[3]) == 0;
-                                } else {
-                                    *(u32x4_u *)(args.out + r.out_off + frame_out_skip<OPEN, FRAME>() +
-                                                 gcm_text_len<OPEN, FRAME>(r)) = tag;
-                                }
-                            }
-                        }
-                    }
                 }
                 g4done = true;
             }
@@ -1419,11 +1334,11 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                 }
                 if (!live)
                     m_lo = m_hi = 0;
-                // (constant-time mode: E(K, J0) waits in the slot of the record's last unit partial, or of the group
+                // (E(K, J0) waits in the slot of the record's last unit partial, or of the group
                 // in a whole-record run, which has no partials)
                 const u32 ekslot = CLDS_PART + 16u * (whole ? threadIdx.x / G : first + unc - 1);
-                gcm_segment<NR, OPEN, 1, FRAME, CT, W8K>(args, lds, rk, iv0, iv1, iv2, r, live, m_lo, m_hi, j, laneoff,
-                                                         tsel_horner, acc, unc == 1, okw, whole, ekslot, W8TREE);
+                gcm_segment<NR, OPEN, FRAME, CT, W8K>(args, lds, rk, iv0, iv1, iv2, r, live, m_lo, m_hi, j, laneoff, tsel_horner,
+                                                      acc, unc == 1, okw, whole, ekslot, W8TREE);
             }
             // from here on everything is read again (run state, descriptor), not carried across the segment
             asm volatile("" ::: "memory");
@@ -1452,32 +1367,17 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                     const u32 mul = unit_mul(gcm_steps<OPEN, FRAME>(r), ulog2, run_unit_cap(args));
                     // last unit of the record: GHASH = Horner over the partials with H^(G * ulen) = (H^(G * ustep))^mul
                     // (whole group)
-                    // (CT: each lane forms the whole product from the same table rows, instead of a share of it from
-                    // its own window rows)
-                    u32x4 g;
-                    if (CT && CT_COMB_TREE_ON && mul == 1) {
-                        g = ct_combine_tree(lds, s_part + first, unc, j);
-                    } else if constexpr (SEG_COOP && COMBINE_SCATTER) {
-                        // (round 5) a scattered chain (ghash.h): each lane carries its dword of the running sum
-                        const GroupWs k = group_ws(tsel_chunk, lane);
-                        const u32 q = j >> 1;
-                        const u32x4 z = {0, 0, 0, 0};
-                        u32 gs = ((const lds_u32 *)(s_part + first))[q];
-                        for (u32 i = 1; i < unc; ++i) {
-                            for (u32 t = 0; t < mul; ++t)  // (mul > 1: huge records only)
-                                gs = gmul_group_ws(lds, gs, k, z, lane);
-                            gs ^= ((const lds_u32 *)(s_part + first + i))[q];
-                        }
-                        g = group_gather(gs, lane);
-                    } else {
-                        g = s_part[first];
-                        for (u32 i = 1; i < unc; ++i) {
-                            g = gmul_combine<CT>(lds, g, tsel_chunk, lane);
-                            for (u32 t = 1; t < mul; ++t)  // huge records only
-                                g = gmul_combine<CT>(lds, g, tsel_chunk, lane);
-                            g ^= s_part[first + i];
-                        }
+                    // (round 5) a scattered chain (ghash.h): each lane carries its dword of the running sum
+                    const GroupWs k = group_ws(tsel_chunk, lane);
+                    const u32 q = j >> 1;
+                    const u32x4 z = {0, 0, 0, 0};
+                    u32 gs = ((const lds_u32 *)(s_part + first))[q];
+                    for (u32 i = 1; i < unc; ++i) {
+                        for (u32 t = 0; t < mul; ++t)  // (mul > 1: huge records only)
+                            gs = gmul_group_ws(lds, gs, k, z, lane);
+                        gs ^= ((const lds_u32 *)(s_part + first + i))[q];
                     }
+                    const u32x4 g = group_gather(gs, lane);
                     const u32x4 tag = g;
                     if (j != G - 1) {
                     } else if (OPEN) {
@@ -1541,7 +1441,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             atomicAdd(&g_ext_runs[blockIdx.x % EXT_RUN_ROWS][EXT == 5 ? 4 : EXT], (unsigned long long)runs_here);
         if (g4_here != 0)
             atomicAdd(&g_ext_runs[blockIdx.x % EXT_RUN_ROWS][7], (unsigned long long)g4_here);
-        if (MK_RUNS && EXT == 5 && mk_here != 0)
+        if (EXT == 5 && mk_here != 0)
             atomicAdd(&g_ext_runs[blockIdx.x % EXT_RUN_ROWS][6], (unsigned long long)mk_here);
     }
     if (kclock != nullptr && threadIdx.x == 0) {  // (vector stores and atomics only)

@@ -28,29 +28,6 @@ __device__ __forceinline__ u32x4 gmul_tab(const lds_u8 *, u32x4 a, u32 tsel)
     return acc;
 }
 
-// a * (table t's power) computed by the G = 8 lanes of a group together (every lane holds a; every lane gets the
-// product): lane j does the four window lookups of nibbles 4j..4j+3 and the group XOR-reduces them.
-__device__ __forceinline__ u32x4 gmul_group(const lds_u8 *, u32x4 a, u32 tsel, u32 j)
-{
-    static_assert(ENGINE_G == 8, "one word half per lane");
-    const u32 q = j >> 1, k0 = 2 * (j & 1);
-    const u32 w = q == 0 ? a[0] : q == 1 ? a[1] : q == 2 ? a[2] : a[3];
-    const u32 hi = w & 0xf0f0f0f0u, lo = (w << 4) & 0xf0f0f0f0u;
-    const u32 base = (8 * q + 2 * k0) * 256;
-    const u32x4 e0 = lds_load128(__builtin_amdgcn_perm(hi, tsel, 0x0c020100u | (4u + k0)) + base);
-    const u32x4 e1 = lds_load128(__builtin_amdgcn_perm(lo, tsel, 0x0c020100u | (4u + k0)) + base + 256);
-    const u32x4 e2 = lds_load128(__builtin_amdgcn_perm(hi, tsel, 0x0c020100u | (5u + k0)) + base + 512);
-    const u32x4 e3 = lds_load128(__builtin_amdgcn_perm(lo, tsel, 0x0c020100u | (5u + k0)) + base + 768);
-    u32x4 r;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        r[c] = xor3(e0[c], e1[c], e2[c]) ^ e3[c];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        r[c] = dpp_xor8(r[c]);
-    return r;
-}
-
 // ------------------------------------------------------------------------------------------------ GHASH (window-major)
 //
 // gmul_tab's tables are nibble-major: entry (window w, nibble n) at T + w * 256 + n * 16, so a ds_read_b128's 16-byte
@@ -59,7 +36,7 @@ __device__ __forceinline__ u32x4 gmul_group(const lds_u8 *, u32x4 a, u32 tsel, u
 // read different rows in one instruction (each lane its own power, or its own windows of a shared product) conflict
 // whenever two of them meet the same nibble: a count that follows the data (profiles/r2_ct_evidence.txt).
 //
-// Window-major tables (H^1..H^7 in slots 0..6 in both modes, the unit combine power in slot 8 in the default mode) put entry
+// Window-major tables (H^1..H^7 in slots 0..6, the unit combine power in slot 8) put entry
 // (w, n) at T + (w >> 4) * 4096 + n * 256 + (w & 15) * 16: the bank group is (w & 15), whatever the data. Lane `lane`
 // of an 8-lane group (index y = lane & 7) handles the four windows 4y..4y+3 of the operand's halfword y, window
 // 4y + (i ^ f) at its i-th lookup, f = (lane >> 2) & 3. At every lookup the 16 lanes of a ds_read_b128 phase (16
@@ -75,7 +52,7 @@ __device__ __forceinline__ u32 wtab_lane_base(u32 T, u32 lane)
 }
 
 // a * (window-major table at tsel) by the G = 8 lanes of a group together (every lane holds a; every lane gets the
-// product): gmul_group's work split, conflict-free (above). tsel is a multiple of 64.
+// product): lane j takes four windows, conflict-free (above), and the group XOR-reduces them. tsel is a multiple of 64.
 __device__ __forceinline__ u32x4 gmul_group_w(const lds_u8 *, u32x4 a, u32 tsel, u32 lane)
 {
     static_assert(ENGINE_G == 8, "one halfword per lane");
@@ -106,100 +83,67 @@ __device__ __forceinline__ u32x4 gmul_group_w(const lds_u8 *, u32x4 a, u32 tsel,
 // bytes 0 and 1, byte 2 of the table base) and byte selector; the lookups' address words B ^ (2k, 2k + 1 window bits)
 // are formed at each multiply (B made opaque there: kept live through the loop, the eight words spilled the kernel).
 //
-// W8_SWAP (round 5): the table sits at LDS address 0, so an address is two bytes: byte 0 the window (operand byte
+// (round 5) The table sits at LDS address 0 (and the AES T-tables at [64K, 128K), aes_tt.h TE_ADDR), so an address is two bytes: byte 0 the window (operand byte
 // (i ^ l), times 16), byte 1 the operand's byte value, bytes 2-3 zero (v_perm's constant selector). The window bytes of
 // lookups 4c..4c+3 are one register, L_c = L_0 ^ 0x40404040 c (bits 6-7 of ((4c + t) ^ l) << 4 are c ^ (l >> 2)), so
 // the 16 addresses cost 16 v_perm and 3 XORs per multiply instead of 16 v_perm and 8 XORs; and the operand's dword swap
 // by bit 2 of l and byte permutation by bits 0-1 merge into one two-source v_perm per dword (4 selects and 4 v_perm
 // instead of 8 and 4): 9 VALU operations fewer per Horner step.
 struct W8Lane {
-    u32 base;  // W8_SWAP: L_0, the window bytes of lookups 0..3; else B
-    u32 psel;  // byte c <- byte c ^ (l & 3) (W8_SWAP: from the pair's other dword when bit 2 of l is set)
+    u32 base;  // L_0, the window bytes of lookups 0..3
+    u32 psel;  // byte c <- byte c ^ (l & 3), from the pair's other dword when bit 2 of l is set
 };
 __device__ __forceinline__ W8Lane w8_lane(u32 lane)
 {
     const u32 l = lane & 15, lb = l & 3;
     // (x * 0x01010101 for a byte x as a v_perm broadcast of byte 0: v_mul_lo_u32 issues at a quarter of the rate)
     auto bcast = [](u32 x) { return __builtin_amdgcn_perm(0u, x, 0u); };
-    if constexpr (W8_SWAP)  // byte t of L_0: (t ^ l) << 4 (l < 16: no carries between bytes)
-        return W8Lane{(bcast(l) ^ 0x03020100u) << 4, (bcast(lb) ^ 0x03020100u) | bcast(l & 4)};
-    return W8Lane{(l << 4) | (l << 12) | ((u32)(LDS_AES_BYTES >> 16) << 16), lb * 0x01010101u ^ 0x03020100u};
+    // byte t of L_0: (t ^ l) << 4 (l < 16: no carries between bytes)
+    return W8Lane{(bcast(l) ^ 0x03020100u) << 4, (bcast(lb) ^ 0x03020100u) | bcast(l & 4)};
 }
-__device__ __forceinline__ u32x4 gmul8(const lds_u8 *, u32x4 t, u32 lane, W8Lane w)
+__device__ __forceinline__ u32x4 gmul8(const lds_u8 *, u32x4 t, W8Lane w)
 {
     asm volatile("" : "+v"(w.base));
-    if constexpr (W8_SWAP) {
-        static_assert(!W8_SWAP || W8_H8_BASE == 0, "the table's address bytes 2-3 are zero");
-        u32 L[4];
+    static_assert(W8_H8_BASE == 0, "the table's address bytes 2-3 are zero");
+    u32 L[4];
 #pragma unroll
-        for (u32 c = 0; c < 4; ++c)
-            L[c] = w.base ^ (c * 0x40404040u);
-        // p[k] byte c = t byte ((4k + c) ^ l): the dword pair by bit 3 of l (selects), then dword k ^ (bit 2 of l) and
-        // the bytes by bits 0-1 in one v_perm of the pair (psel picks from the other dword when bit 2 is set)
-        u32 a0, a1, a2, a3;
-#if GMUL8_CONST_MASK  // (the W8_SWAP form: the other one reads the lane index)
-        // (round 5) the selects by bit 3 of the lane take a constant lane mask (lanes 8-15 of every 16:
-        // 0xff00ff00ff00ff00) in VCC instead of a compare of the lane index, which the loop re-derived every step
-        // (v_mbcnt x2, v_and, v_cmp: the kernel is short of SGPRs to keep the mask)
-        (void)lane;
-        asm("s_mov_b32 vcc_lo, 0xff00ff00\n\t"
-            "s_mov_b32 vcc_hi, 0xff00ff00\n\t"
-            "v_cndmask_b32 %0, %4, %6, vcc\n\t"
-            "v_cndmask_b32 %1, %5, %7, vcc\n\t"
-            "v_cndmask_b32 %2, %6, %4, vcc\n\t"
-            "v_cndmask_b32 %3, %7, %5, vcc"
-            : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3)
-            : "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3])
-            : "vcc");
-#else
-        const bool s2 = (lane & 8) != 0;
-        a0 = s2 ? t[2] : t[0], a1 = s2 ? t[3] : t[1], a2 = s2 ? t[0] : t[2], a3 = s2 ? t[1] : t[3];
-#endif
-        u32 p[4] = {__builtin_amdgcn_perm(a1, a0, w.psel), __builtin_amdgcn_perm(a0, a1, w.psel),
-                    __builtin_amdgcn_perm(a3, a2, w.psel), __builtin_amdgcn_perm(a2, a3, w.psel)};
-        if (CT_PROBE_CONST)
-            p[0] = p[1] = p[2] = p[3] = 0;
-        u32x4 acc = {0, 0, 0, 0};
-#pragma unroll
-        for (u32 i = 0; i < 16; i += 2) {
-            const u32 c = i >> 2, b = i & 3;
-            const u32x4 e0 = lds_load128(__builtin_amdgcn_perm(p[c], L[c], 0x0c0c0000u | ((4u + b) << 8) | b));
-            const u32x4 e1 = lds_load128(__builtin_amdgcn_perm(p[c], L[c], 0x0c0c0000u | ((5u + b) << 8) | (b + 1)));
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                acc[k] = xor3(acc[k], e0[k], e1[k]);
-        }
-        return acc;
-    }
-    u32 wreg[8];
-#pragma unroll
-    for (u32 k = 0; k < 8; ++k)
-        wreg[k] = w.base ^ (((2 * k) << 4) | ((2 * k + 1) << 12));
-    static_assert(LDS_AES_BYTES == 0x10000, "the table base is byte 2 of the address");
-    const u32 l = lane & 15;
-    const bool s2 = (l & 8) != 0, s1 = (l & 4) != 0;
-    const u32 a0 = s2 ? t[2] : t[0], a1 = s2 ? t[3] : t[1], a2 = s2 ? t[0] : t[2], a3 = s2 ? t[1] : t[3];
-    const u32 b[4] = {s1 ? a1 : a0, s1 ? a0 : a1, s1 ? a3 : a2, s1 ? a2 : a3};
-    u32 p[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        p[k] = __builtin_amdgcn_perm(b[k], b[k], w.psel);  // byte c <- byte c ^ (l & 3)
+    for (u32 c = 0; c < 4; ++c)
+        L[c] = w.base ^ (c * 0x40404040u);
+    // p[k] byte c = t byte ((4k + c) ^ l): the dword pair by bit 3 of l (selects), then dword k ^ (bit 2 of l) and
+    // the bytes by bits 0-1 in one v_perm of the pair (psel picks from the other dword when bit 2 is set)
+    u32 a0, a1, a2, a3;
+    // (round 5) the selects by bit 3 of the lane take a constant lane mask (lanes 8-15 of every 16:
+    // 0xff00ff00ff00ff00) in VCC instead of a compare of the lane index, which the loop re-derived every step
+    // (v_mbcnt x2, v_and, v_cmp: the kernel is short of SGPRs to keep the mask)
+    asm("s_mov_b32 vcc_lo, 0xff00ff00\n\t"
+        "s_mov_b32 vcc_hi, 0xff00ff00\n\t"
+        "v_cndmask_b32 %0, %4, %6, vcc\n\t"
+        "v_cndmask_b32 %1, %5, %7, vcc\n\t"
+        "v_cndmask_b32 %2, %6, %4, vcc\n\t"
+        "v_cndmask_b32 %3, %7, %5, vcc"
+        : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3)
+        : "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3])
+        : "vcc");
+    u32 p[4] = {__builtin_amdgcn_perm(a1, a0, w.psel), __builtin_amdgcn_perm(a0, a1, w.psel),
+                __builtin_amdgcn_perm(a3, a2, w.psel), __builtin_amdgcn_perm(a2, a3, w.psel)};
+    if (CT_PROBE_CONST)
+        p[0] = p[1] = p[2] = p[3] = 0;
     u32x4 acc = {0, 0, 0, 0};
 #pragma unroll
     for (u32 i = 0; i < 16; i += 2) {
-        const u32x4 e0 = lds_load128(__builtin_amdgcn_perm(p[i >> 2], wreg[i >> 1], 0x0c020000u | ((4u + (i & 3)) << 8)));
-        const u32x4 e1 =
-            lds_load128(__builtin_amdgcn_perm(p[i >> 2], wreg[i >> 1], 0x0c020001u | ((4u + ((i + 1) & 3)) << 8)));
+        const u32 c = i >> 2, b = i & 3;
+        const u32x4 e0 = lds_load128(__builtin_amdgcn_perm(p[c], L[c], 0x0c0c0000u | ((4u + b) << 8) | b));
+        const u32x4 e1 = lds_load128(__builtin_amdgcn_perm(p[c], L[c], 0x0c0c0000u | ((5u + b) << 8) | (b + 1)));
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-            acc[c] = xor3(acc[c], e0[c], e1[c]);
+        for (int k = 0; k < 4; ++k)
+            acc[k] = xor3(acc[k], e0[k], e1[k]);
     }
     return acc;
 }
 
 // ------------------------------------------------------------------------------------------------ GHASH (multi-key runs)
 //
-// (round 6) Multi-key whole runs (MK runs, gcm_chunked_kernel EXT 4): the short records of up to MK_SLOTS connections
+// (round 6) Multi-key whole runs (MK runs, gcm_chunked_kernel EXT 5): the short records of up to MK_SLOTS connections
 // share one run, each connection's tables in a 16 KiB slot of the W8 map's [0, 64K): H^4 (the 4-lane Horner power) and H
 // (the segment end, w8_lane_end4), both 4-bit window-major (entry (w, n) at T + (w >> 4) * 4096 + n * 256 + (w & 15) *
 // 16, T = slot << 14). gmul4w is gmul8's scheme on that 4-bit table: lane l = lane & 15 takes window i ^ l at its i-th
@@ -207,7 +151,7 @@ __device__ __forceinline__ u32x4 gmul8(const lds_u8 *, u32x4 t, u32 lane, W8Lane
 // slots (the slot is address bits 14-15): 32 conflict-free lookups per multiply instead of 16, in exchange for a table a
 // quarter of the 8-bit one's size. The operand is spread once per multiply into eight "nibble bytes" registers R[c]
 // (byte b of R[c] = nibble of window (4c + b) ^ l, with the slot's address bits above it), so a lookup's address is one
-// v_perm of R[c] and the window bytes L (gmul8's W8_SWAP form), as in gmul8.
+// v_perm of R[c] and the window bytes L, as in gmul8.
 struct MK4Lane {
     u32 s0, s1;  // v_perm selectors of R[2k], R[2k + 1] from (hi_k, lo_k) for this lane's bits 0-2
 };
@@ -229,10 +173,10 @@ __device__ __forceinline__ MK4Lane mk4_lane(u32 lane)
     }
     return MK4Lane{s[0], s[1]};
 }
-// t * (the 4-bit window-major table of slot `slot`) for this lane (W8Lane w: the window bytes L_0, W8_SWAP)
+// t * (the 4-bit window-major table of slot `slot`) for this lane (W8Lane w: the window bytes L_0)
 __device__ __forceinline__ u32x4 gmul4w(const lds_u8 *, u32x4 t, W8Lane w, MK4Lane m, u32 kslot)
 {
-    static_assert(W8_SWAP, "the window bytes of gmul8's W8_SWAP form");
+    static_assert(W8_H8_BASE == 0, "the window bytes of gmul8");
     asm volatile("" : "+v"(w.base), "+v"(m.s0), "+v"(m.s1));
     u32 L[4];
 #pragma unroll
@@ -260,7 +204,7 @@ __device__ __forceinline__ u32x4 gmul4w(const lds_u8 *, u32x4 t, W8Lane w, MK4La
     if (CT_PROBE_CONST)
 #pragma unroll
         for (u32 c = 0; c < 8; ++c)
-            R[c] = kslot * 0x01010101u;
+            R[c] = kslot;  // (mk_kslot replicates the slot bits into every byte)
     u32x4 acc = {0, 0, 0, 0};
 #pragma unroll
     for (u32 i = 0; i < 32; i += 2) {
@@ -274,21 +218,14 @@ __device__ __forceinline__ u32x4 gmul4w(const lds_u8 *, u32x4 t, W8Lane w, MK4La
     return acc;
 }
 
-// A group's product by the unit combine power (table 8) or another combine element: with SEG_COOP gmul_group_w
-// (window-major, conflict-free by construction) in both modes; without it, the constant-time mode gmul_tab (every lane
-// the whole product from the same rows of a nibble-major table) and the default mode gmul_group
-template <bool CT>
+// A group's product by the unit combine power (table 8) or another combine element: gmul_group_w (window-major,
+// conflict-free by construction)
 __device__ __forceinline__ u32x4 gmul_combine(const lds_u8 *lds, u32x4 a, u32 tsel, u32 lane)
 {
-    if constexpr (SEG_COOP)
-        return gmul_group_w(lds, a, tsel, lane);
-    else if constexpr (CT)
-        return gmul_tab(lds, a, tsel);
-    else
-        return gmul_group(lds, a, tsel, lane % ENGINE_G);
+    return gmul_group_w(lds, a, tsel, lane);
 }
 
-// The segment end (gcm_segment, both modes): lane j of a group holds a_j, its partial with its last stream position
+// The segment end (gcm_segment): lane j of a group holds a_j, its partial with its last stream position
 // unmultiplied, and owes it the power H^(e_j), e_j = 8 - rank_j (the ranks are the lanes rotated by rot, uniform over the
 // group). Returns this lane's share of sum_j a_j H^(e_j - 1) (the caller XOR-reduces the group and multiplies the sum by
 // H): the value of rank r moves to lane r (ds_bpermute, only when some group of the wave has rot != 0), an 8 x 8

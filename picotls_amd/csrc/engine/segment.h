@@ -4,16 +4,16 @@
 #define PTLS_MI355X_ENGINE_SEGMENT_H
 
 // GHASH/CTR work of one G-lane group on steps [m_lo, m_hi) of record r's stream (see file header): lane j owns stream
-// positions j + G*m and runs them NB at a time. The NB AES-CTR blocks of a step are independent (NB x 16 LDS lookups
-// per round in flight); their GHASH folds stay sequential (Horner with H^G; each lane's last position in the segment
-// with H^(end - position), from its own table). On return every lane of the group holds the segment's GHASH partial
-// sum(X_i * H^(end - i)), plus E(K, J0) when the segment holds the record's length block: the length lane (lane
-// (N - 1) mod G) encrypts J0 in that step and XORs it into its accumulator after its last multiply (the length block is
-// the last stream position, H^0 in every later combine), so a finished record's GHASH sum is its tag, and E(K, J0)
-// need not stay live through the loop (it was spilled to scratch once per segment); with CT only the length lane's
-// partial includes it. Invalid groups pass m_lo == m_hi. With finish (a whole record), a seal writes the tag and an open
-// returns the tag check in okw on the length lane (1 = verified, 0 = not; 2 on every other lane and without finish):
-// the caller stores the ok byte, so the record's batch index need not stay live through the segment.
+// positions j + G*m, one AES-CTR block per step (16 LDS lookups per round in flight); its GHASH folds are sequential
+// (Horner with H^G; each lane's last position in the segment takes H^(end - position) after the loop). On return every
+// lane of the group holds the segment's GHASH partial sum(X_i * H^(end - i)), plus E(K, J0) when the segment holds the
+// record's length block: the length lane (lane (N - 1) mod G) encrypts J0 in that step and XORs it into its
+// accumulator after the segment end (the length block is the last stream position, H^0 in every later combine), so a
+// finished record's GHASH sum is its tag, and E(K, J0) need not stay live through the loop (it waits in the caller's
+// LDS slot; live, it was spilled to scratch once per segment). Invalid groups pass m_lo == m_hi.
+// With finish (a whole record), a seal writes the tag and an open returns the tag check in okw on the length lane (1 =
+// verified, 0 = not; 2 on every other lane and without finish): the caller stores the ok byte, so the record's batch
+// index need not stay live through the segment.
 //
 // Stream layout. Units of the chunked schedule end on step boundaries, so their stream [zero padding | AAD | text |
 // length] is front-padded to a multiple of G positions (N = G * K). A whole record (ALIGNED: the lockstep kernel and the
@@ -22,18 +22,17 @@
 // writes and 2 % of seal time on 16 KiB records, profiles/r2_write_align.txt). Its stream ends where it ends (N any):
 // lanes past the length block in the last step are idle, and each lane's last position p multiplies by H^(N - p), 1..G.
 //
-// Segment end (SEG_COOP, both modes, late round 3): a lane's last multiply by its own power H^e from its own
-// nibble-major table read another table row than the lanes beside it, so its bank conflicts depended on the data
-// (profiles/r2_ct_counters.txt). Now every lane keeps its last position unmultiplied, the wave's last step skips the
-// Horner multiply, and coop_last_powers (ghash.h) applies the powers from window-major tables after the loop: 32
-// conflict-free lookups per lane, E(K, J0) waiting in the caller's LDS slot (ekslot) and added on the length lane.
-// Without SEG_COOP: CT (constant-time LDS access) with CT_TREE (round 3), every step multiplies by the uniform Horner table, a lane's last position stays unmultiplied, and
-// after the loop a butterfly over the group's lanes applies the powers H^e (three levels with the tables H, H^2, H^4,
-// then H once more: four uniform-table multiplies per segment). E(K, J0) then waits in an LDS slot of the caller's
-// (ekslot) until the tree is done, and is added on the length lane only (lane jl: the lane the tag or the unit partial
-// is taken from). The round-2 form (CT_TREE 0) ran four multiplies, H^8, H^4, H^2, H^1 kept on the bits of e, in every
-// step in which some lane of the wave was at its last position (two or more steps per segment).
-template <int NR, bool OPEN, int NB, int FRAME = 0, bool CT = false, bool W8 = false, int GG = ENGINE_G, bool MK4 = false>
+// Segment end (late round 3): a lane's last multiply by its own power H^e from its own nibble-major table read another
+// table row than the lanes beside it, so its bank conflicts depended on the data (profiles/r2_ct_counters.txt). Now
+// every lane keeps its last position unmultiplied, the wave's last step skips the Horner multiply, and
+// coop_last_powers (ghash.h) applies the powers from window-major tables after the loop: 32 conflict-free lookups per
+// lane, E(K, J0) waiting in the caller's LDS slot (ekslot) and added on the length lane. (The per-lane last multiply,
+// the round-3 butterfly over uniform tables and the round-2 four-multiply step it replaced are no longer in the source.)
+// CT (the kernels' constant-time argument, instantiated true by the chunked, spread and span kernels and false by the
+// lockstep one) is read nowhere since the segment ends became one: it only keeps the lockstep kernel's instantiation
+// apart from the spread and span kernels'. Sharing one, the step lambdas below gain callers, the compiler inlines them
+// otherwise, and the four lockstep kernels' code changes (21 to 38 lines each).
+template <int NR, bool OPEN, int FRAME = 0, bool CT = false, bool W8 = false, int GG = ENGINE_G, bool MK4 = false>
 __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 *lds, const u32 (&rk)[NR + 1][4], u32 iv0,
                                             u32 iv1, u32 iv2, const ptls_mi355x_record_t &r, bool valid, u32 m_lo,
                                             u32 m_hi, u32 j, u32 laneoff, u32 tsel_horner, u32x4 &acc, bool finish,
@@ -50,8 +49,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     constexpr int GS = G == 8 ? 3 : 2;  // log2 G
     // W8 (a W8 run of the pair's EXT 3 kernel, gcm_chunked_kernel): Horner on the 8-bit H^8 table (gmul8), the lanes'
     // last powers by a serial Horner over the group's ranks with the window-major H table (W8_TAB_H, w8_lane_end)
-    constexpr bool COOP = SEG_COOP && !W8;  // the conflict-free segment end (coop_last_powers), both modes
-    constexpr bool TREE = !W8 && !SEG_COOP && CT && CT_TREE;
+    // (without W8: Horner on the nibble-major H^8 table, the conflict-free segment end coop_last_powers)
     W8Lane w8 = {};
     if constexpr (W8)
         w8 = w8_lane(lane_here());
@@ -65,7 +63,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         if constexpr (MK4)
             return gmul4w(lds, t, w8, mk4, mk_kslot);
         else
-            return gmul8(lds, t, GMUL8_LANE(), w8);
+            return gmul8(lds, t, w8);
     };
     constexpr bool SEAL_FRAME = FRAME == 1 && !OPEN, OPEN_FRAME = FRAME == 1 && OPEN, TLS12 = FRAME == 2;
     const u32 L = gcm_text_len<OPEN, FRAME>(r), A = gcm_aad_len<OPEN, FRAME>(r);
@@ -82,8 +80,8 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         P = (int)(((u32)((uintptr_t)dst >> 4) - na) & (G - 1));
         // (round 6) a 4-lane open puts text block 0 at a step's start instead: the steps before it need no keystream
         // (the seal's aligned output gives it the same padding), and the steady steps hold their blocks until a line is
-        // whole (G4_LINE_HOLD)
-        if constexpr (G4_OPEN_TEXT_STEPS && OPEN && G == 4)
+        // whole (LINE below)
+        if constexpr (OPEN && G == 4)
             P = (int)((0u - na) & (G - 1));
         // ... unless that costs a record shorter than ALIGN_MIN_STEPS steps one more step (its wave would take it too:
         // -6 % on 1200-byte records), which keeps the padding of a multiple of G positions
@@ -102,7 +100,6 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     const bool at_end = aligned;
     const int m_last = !valid ? -1 : at_end ? ((int)N - 1 - (int)j) >> GS : (int)m_hi - 1;
     const u32 e_last = at_end ? N - ((u32)G * (u32)m_last + j) : (u32)G - j;  // 1..G
-    const u32 tsel_last = 0x10000u + (e_last - 1) * GHASH_TABLE_BYTES;
     // the first step in which some lane of the group is at its last position (the steady range ends before it)
     const int m_first_last = at_end ? ((int)N - G) >> GS : (int)m_hi - 1;
     const u32 jl = (N - 1) & (G - 1);  // the length block's lane
@@ -124,8 +121,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
 
     acc = u32x4{0, 0, 0, 0};
 
-    static_assert(NB == 1, "the counter cache runs one block per lane and step");
-    CtrCache1 cc1 = {};
+    CtrCache1 cc1 = {};  // (the counter cache runs one block per lane and step)
     u32 cc1_key = 0xffffffffu;  // counter >> 8 of the cached window (none yet)
 
     // data block of lane j at step m: b = j + G*m - P - na; a full 16-byte input block is loaded one step ahead, so
@@ -134,23 +130,25 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         b = (int)(j + G * m) - P - (int)na;
         return m < m_hi && b >= 0 && b < (int)nb && Lsrc - 16u * (u32)b >= 16;
     };
-    u32x4 nxt[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
+    // (a loop of one trip, what the loop over the blocks of a step left: written as a plain block, the compiler nests
+    // the load's branches and every kernel's code changes)
+    u32x4 nxt = {0, 0, 0, 0};
+    for (int i = 0; i < 1; ++i) {
         int b;
-        nxt[i] = u32x4{0, 0, 0, 0};
-        if (full_block(m_lo + i, b))
-            nxt[i] = *(const u32x4_u *)(src + 16u * (u32)b);
+        if (full_block(m_lo, b))
+            nxt = *(const u32x4_u *)(src + 16u * (u32)b);
     }
 
     // step m, part 1: the next step's input prefetch and this step's counter block (refreshing the counter cache when
-    // the lane enters a new 256-counter window)
+    // the lane enters a new 256-counter window). (Round 5: the W8 kernels' unframed steps outside the steady range as one
+    // pass, the non-text inputs loaded ahead of the AES, measured within +-0.5 % of these two parts on quic1200 and
+    // mixed, profiles/r5/g4_ab.txt, and was not kept.)
     u32x4 cur;
     auto setup_step = [&](u32 m0, u32 (&st)[1][4], bool wave_ks) {
-        cur = nxt[0];
+        cur = nxt;
         int bn;
         if (full_block(m0 + 1, bn))
-            nxt[0] = *(const u32x4_u *)(src + 16u * (u32)bn);
+            nxt = *(const u32x4_u *)(src + 16u * (u32)bn);
         // AES-CTR input: data positions encrypt counter 2+b, all others J0 (kept by the length lane as E(K, J0))
         const int logical = (int)(j + G * m0) - P;
         const int b = logical - (int)na;
@@ -165,7 +163,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     };
     // step m, part 2: with the keystream block ks, write the output and return the GHASH input block X of position
     // j + G*m
-    auto finish_step = [&](u32 m, const u32x4 &ks, u32x4 &ek0) -> u32x4 {
+    auto finish_step = [&](u32 m, const u32x4 &ks) -> u32x4 {
         const bool act = m < m_hi;
         const int logical = (int)(j + G * m) - P;
         const int b = logical - (int)na;
@@ -173,7 +171,6 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         const bool is_aad = act && logical >= 0 && logical < (int)na;
         const bool is_len = act && logical == (int)(na + nb);
         u32x4 X = {0, 0, 0, 0};
-#if ENGINE_FAST_STEP
         // steady state: every active lane of the wave holds a full 16-byte text block (one uniform branch, no
         // per-case dispatch)
         const bool full = is_data && Lsrc - 16u * (u32)b >= 16;
@@ -183,7 +180,6 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
                 *(u32x4_u *)(dst + 16u * (u32)b) = o;
             return OPEN ? cur : o;
         }
-#endif
         if (is_data) {
             const u32 rem = L - 16u * (u32)b;
             uint8_t *op = dst + 16u * (u32)b;
@@ -233,10 +229,8 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
             X[1] = bswap32((u32)abits);
             X[2] = bswap32((u32)(cbits >> 32));
             X[3] = bswap32((u32)cbits);
-            if (COOP || TREE || W8)  // (kept in LDS until after the loop: live through it, it was spilled)
-                *(lds_u32x4 *)(const_cast<lds_u8 *>(lds) + ekslot) = ks;
-            else
-                ek0 = ks;
+            // (E(K, J0) kept in LDS until after the loop: live through it, it was spilled)
+            *(lds_u32x4 *)(const_cast<lds_u8 *>(lds) + ekslot) = ks;
         }
         return X;
     };
@@ -263,7 +257,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         if constexpr (TREE_PRIO_BAND && W8) {
             if (w8tree) {
                 const u32 q = left / TREE_PRIO_BAND;
-                const u32 lvl = TREE_PRIO_INV ? (q >= 3 ? 0u : 3u - q) : (q >= 3 ? 3u : q);
+                const u32 lvl = q >= 3 ? 3u : q;
                 if (lvl == 3)
                     __builtin_amdgcn_s_setprio(3);
                 else if (lvl == 2)
@@ -301,12 +295,14 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
             const int b0 = (int)(j + G * (m_lo + (u32)sa)) - D0;  // this lane's text block at step sa
             u32 off = 16u * (u32)b0;                               // its byte offset in the text
             u32 ctr = (u32)b0 + 2;
-            // G4_PAIR_STORES: the block held from the previous step (the first half of its line), stored with this one
-            constexpr bool LINE = G4_LINE_HOLD && G4_OPEN_TEXT_STEPS && OPEN && G == 4;
-            constexpr bool PAIR = G4_PAIR_STORES && G == 4 && !LINE;
+            // PAIR (a 4-lane seal): the block held from the previous step (the first half of its line), stored with this
+            // one. Half lines stored a step apart leave the L2 as two write-backs of the line (tools/mb/wcal.hip:
+            // 1.07-1.08x the bytes; paired, 1.00x)
+            constexpr bool LINE = OPEN && G == 4;
+            constexpr bool PAIR = G == 4 && !LINE;
             u32x4 held = {0, 0, 0, 0};
             bool have = false;
-            // G4_LINE_HOLD (a 4-lane open, its steps aligned to the text, not to the output): held = the lane's block
+            // LINE (a 4-lane open, its steps aligned to the text, not to the output): held = the lane's block
             // in a line's first half, held2 its block in the second half (the next step's). The line is whole at the
             // second half's step, or one step later for a lane past its first half's line offset ("late": j >
             // (dst + off) / 16 mod 4, the line's last block falls in the next step); then the lane stores both. Late
@@ -318,17 +314,17 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
                 late = j > (((u32)(uintptr_t)(dst + off) >> 4) & 3u);
                 dst_l = dst - (late ? 64 : 0);
             }
-            // G8_PAIR_STORES: a group whose steps straddle lines (a cut run's unit, counted from the stream's end) --
+            // pair8: an 8-lane group whose steps straddle lines (a cut run's unit, counted from the stream's end) --
             // the lanes past the line boundary (the same lanes every step) hold their blocks one step, so each line is
             // stored by one step's instructions; uniform over the wave: no lane straddles in an aligned stream
             const bool holder = G == 8 && ((u32)(uintptr_t)(dst + off) & 127u) < 16u * j;
             // (unframed batches: the TLS-framed kernels measured slower with it, TLS 1.2 1200-byte seal -1.4 %)
-            const bool pair8 = G8_PAIR_STORES && G == 8 && W8 && FRAME == 0 && !aligned && __any(holder);
+            const bool pair8 = G == 8 && W8 && FRAME == 0 && !aligned && __any(holder);
             for (int s = sa; s < sb; ++s) {
                 if ((s & 3) == 0)
                     progress_prio(Smax - (u32)s);
-                cur = nxt[0];
-                nxt[0] = *(const u32x4_u *)(src + off + 16 * G);
+                cur = nxt;
+                nxt = *(const u32x4_u *)(src + off + 16 * G);
                 u32 st[1][4] = {{n0, n1, n2, bswap32(ctr) ^ rk[0][3]}};
                 if ((ctr >> 8) != cc1_key) {
                     cc1 = ctr_cache1_init<NR>(lds, laneoff, rk, n0, n1, n2, st[0][3]);
@@ -395,146 +391,41 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
             tsteady += stamp() - tst0;
 #endif
         }
-#if W8_LEAN_STEP
-        if constexpr (W8 && FRAME == 0) {
-            // (round 5) the W8 kernels' steps outside the steady range, unframed: every input that is not a full text
-            // block (the AAD block, the record's partial last text block) is loaded before the AES, where its latency
-            // hides, and the output cases are one chain of exec-masked branches instead of the per-case dispatch
-            const u32 m0 = m_lo + s0;
-            const bool act = m0 < m_hi;
-            const int logical = (int)(j + G * m0) - P;
-            const int b = logical - (int)na;
-            const bool is_data = act && logical >= (int)na && b < (int)nb;
-            const bool is_aad = act && logical >= 0 && logical < (int)na;
-            const bool is_len = act && logical == (int)(na + nb);
-            const u32 rem = L - 16u * (u32)b;  // (data positions)
-            const bool full = is_data && rem >= 16;
-            u32x4 xin = nxt[0];
-            int bn;
-            if (full_block(m0 + 1, bn))
-                nxt[0] = *(const u32x4_u *)(src + 16u * (u32)bn);
-            // (masked after the AES: a mask here would wait for the load before it)
-            u32 nin = 16;
-            if (is_aad) {
-                const u32 arem = A - 16u * (u32)logical;
-                const uint8_t *ap = aadp + 16u * (u32)logical;
-                xin = arem >= 16 ? *(const u32x4_u *)ap : load_partial_raw(ap, arem);
-                nin = min(arem, 16u);
-            } else if (is_data && !full) {
-                xin = load_partial_raw(src + 16u * (u32)b, rem);
-                nin = rem;
-            }
-            // AES-CTR input: data positions encrypt counter 2 + b, all others J0 (the length lane keeps E(K, J0))
-            const u32 ctr = is_data ? (u32)(b + 2) : 1u;
-            u32 st[1][4] = {{n0, n1, n2, bswap32(ctr) ^ rk[0][3]}};
-            if ((ctr >> 8) != cc1_key) {
-                cc1 = ctr_cache1_init<NR>(lds, laneoff, rk, n0, n1, n2, st[0][3]);
-                cc1_key = ctr >> 8;
-            }
-            aes_ctr_cached1<NR>(lds, laneoff, rk, cc1, st);
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 ks = {st[0][0], st[0][1], st[0][2], st[0][3]};
-            u32x4 X = {0, 0, 0, 0};
-            if (full) {
-                const u32x4 o = xin ^ ks;
-                *(u32x4_u *)(dst + 16u * (u32)b) = o;
-                X = OPEN ? xin : o;
-            } else if (is_aad) {
-                X = mask_tail(xin, nin);
-            } else if (is_data) {
-                const u32x4 v = mask_tail(xin, nin);
-                const u32x4 o = mask_tail(v ^ ks, rem);
-                store_partial(dst + 16u * (u32)b, o, rem);
-                X = OPEN ? v : o;
-            } else if (is_len) {
-                u32 Ah = A, Lh = L;
-                asm volatile("" : "+v"(Ah), "+v"(Lh));
-                const u64 abits = (u64)Ah * 8, cbits = (u64)Lh * 8;
-                X = u32x4{bswap32((u32)(abits >> 32)), bswap32((u32)abits), bswap32((u32)(cbits >> 32)),
-                          bswap32((u32)cbits)};
-                *(lds_u32x4 *)(const_cast<lds_u8 *>(lds) + ekslot) = ks;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // Horner with H^8 except at the lane's last position (its power comes in w8_lane_end); none in the wave's
-            // last step
-            const u32x4 t = acc ^ X;
-            u32x4 prod = t;
-            if (s0 + 1 < Smax) {
-                prod = horner(t);
-                if ((int)m0 == m_last)
-                    prod = t;
-            }
-            if ((int)m0 <= m_last)
-                acc = prod;
-            __builtin_amdgcn_sched_barrier(0);
-            continue;
-        }
-#endif
         const u32 m0 = m_lo + s0;
         // (round 5) a step in which no lane of the wave holds a text or length position (front padding and AAD only:
         // the first step of 4-lane groups on short records) needs no keystream and skips the AES; the lengths decide
         // it, not the data
         const int lg = (int)(j + G * m0) - P;
         // (4-lane groups only: in 8-lane kernels such a step is rare, and the test cost the TLS 1.3 open kernel spills)
-        const bool wave_ks = !(SKIP_EMPTY_AES && G == 4) || __any(m0 < m_hi && lg >= (int)na && lg <= (int)(na + nb)) != 0;
+        const bool wave_ks = G != 4 || __any(m0 < m_hi && lg >= (int)na && lg <= (int)(na + nb)) != 0;
         u32 st[1][4];
         setup_step(m0, st, wave_ks);
         if (wave_ks)
             aes_ctr_cached1<NR>(lds, laneoff, rk, cc1, st);
         __builtin_amdgcn_sched_barrier(0);
-        u32x4 ek0 = {0, 0, 0, 0};
-        const u32x4 X = finish_step(m0, u32x4{st[0][0], st[0][1], st[0][2], st[0][3]}, ek0);
+        const u32x4 X = finish_step(m0, u32x4{st[0][0], st[0][1], st[0][2], st[0][3]});
         // scheduling fence: keeps the 32 table loads of this fold from being hoisted next to the other work (that
         // hoisting spills them to scratch)
         __builtin_amdgcn_sched_barrier(0);
         const bool last_here = (int)m0 == m_last;
-        u32x4 prod;
-        if (!W8 && !COOP && CT && CT_TREE) {
-            // every lane multiplies by H^8, the uniform Horner table; a lane's last position stays unmultiplied and
-            // takes its power H^e_last in the tree after the loop
-            const u32x4 t = acc ^ X;
-            prod = gmul_tab(lds, t, tsel_horner);
+        // every lane multiplies by H^G, the uniform Horner table, except at its last position, which takes its power
+        // H^e_last after the loop (coop_last_powers, w8_lane_end); in the wave's last step no lane needs the multiply
+        const u32x4 t = acc ^ X;
+        u32x4 prod = t;
+        if (s0 + 1 < Smax) {
+            if constexpr (W8)
+                prod = horner(t);
+            else
+                prod = gmul_tab(lds, t, tsel_horner);
             if (last_here)
                 prod = t;
-        } else if (!W8 && !COOP && CT && __any(last_here)) {
-            // H^8 (the Horner step, and a last power of 8), then H^4, H^2, H^1 kept on the bits of e_last; one
-            // multiply site in a loop, so the branch costs no more registers than a plain step
-            u32x4 t = acc ^ X;
-            prod = t;
-#pragma unroll 1
-            for (u32 it = 0; it < 4; ++it) {
-                const u32x4 q = gmul_tab(lds, t, 0x10000u + ((8u >> it) - 1u) * GHASH_TABLE_BYTES);
-                if (it == 0)
-                    prod = q;
-                else if (e_last & (8u >> it))
-                    t = q;
-            }
-            if (!last_here || e_last == (u32)G)
-                t = prod;
-            prod = t;
-        } else if (COOP || W8) {
-            // every lane multiplies by H^8, the uniform Horner table, except at its last position, which takes its
-            // power H^e_last after the loop (coop_last_powers); in the wave's last step no lane needs the multiply
-            const u32x4 t = acc ^ X;
-            prod = t;
-            if (s0 + 1 < Smax) {
-                if constexpr (W8)
-                    prod = horner(t);
-                else
-                    prod = gmul_tab(lds, t, tsel_horner);
-                if (last_here)
-                    prod = t;
-            }
-        } else {
-            prod = gmul_tab(lds, acc ^ X, !CT && last_here ? tsel_last : tsel_horner);
         }
         if ((int)m0 <= m_last)
-            acc = prod ^ ek0;
+            acc = prod;
         __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (PROGRESS_PRIO && W8)
-        if (!w8tree || TREE_PRIO_BAND)
-            __builtin_amdgcn_s_setprio(0);
+    if constexpr ((PROGRESS_PRIO != 0 || TREE_PRIO_BAND != 0) && W8)
+        __builtin_amdgcn_s_setprio(0);
 #if ENGINE_PROFILE
     const unsigned long long tsg2 = stamp();
 #endif
@@ -559,43 +450,16 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
             acc = w8_lane_end(lds, acc, lane_here(), rank);
         if (valid && m_hi * G >= N && j == jl)  // the segment holds the length block: E(K, J0), on its lane
             acc ^= u32x4(*(const lds_u32x4 *)(lds + ekslot));
-    } else if constexpr (TREE) {
-        // sum over the group of a_l H^(e_l) (a_l: lane l's partial with its last position unmultiplied, e_l in 1..8 a
-        // permutation over the lanes), as a butterfly over the ranks t = 8 - e: level k pairs rank t (bit k clear) with
-        // rank t + k as v_t H^k + v_(t+k); every lane multiplies by the same table (H, H^2, H^4, then H once more) and
-        // takes its partner's product or value through the crossbar. Lane l holds rank (l - rot) mod 8.
-        const u32 lane = lane_here();
-        const u32 rank = valid ? (u32)G - e_last : j;
-        const u32 rot = (j - rank) & (G - 1);
-        u32x4 v = acc;
-#pragma unroll 1
-        for (u32 lv = 0; lv < 3; ++lv) {
-            const u32 k = 1u << lv;
-            const u32x4 y = gmul_tab(lds, v, 0x10000u + (k - 1u) * GHASH_TABLE_BYTES);  // H^k
-            const bool hi = (rank & k) != 0;
-            const u32x4 send = hi ? v : y;
-            const int src = (int)(((lane & ~(u32)(G - 1)) | (((rank ^ k) + rot) & (G - 1))) * 4);
-            u32x4 recv;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                recv[c] = (u32)__builtin_amdgcn_ds_bpermute(src, (int)send[c]);
-            v = hi ? (recv ^ v) : (y ^ recv);
-        }
-        acc = gmul_tab(lds, v, 0x10000u);  // * H
-        if (valid && m_hi * G >= N && j == jl)  // the segment holds the length block: E(K, J0), on its lane
-            acc ^= u32x4(*(const lds_u32x4 *)(lds + ekslot));
     } else {
-        if constexpr (COOP) {  // the lanes' powers H^(e_last - 1), conflict-free (ghash.h); ranks rotated by N mod 8
-            const u32 rank = valid ? (u32)G - e_last : j;
-            acc = coop_last_powers(lds, acc, lane_here(), (j - rank) & (G - 1));
-        }
+        // the lanes' powers H^(e_last - 1), conflict-free (ghash.h); ranks rotated by N mod 8
+        const u32 rank = valid ? (u32)G - e_last : j;
+        acc = coop_last_powers(lds, acc, lane_here(), (j - rank) & (G - 1));
         // XOR over the G lanes of the group
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             acc[c] = dpp_xor8(acc[c]);
-        if constexpr (COOP)  // the group's sum times H (table 0, window-major)
-            acc = gmul_group_w(lds, acc, LDS_AES_BYTES, lane_here());
-        if (COOP && valid && m_hi * G >= N && j == jl)  // the segment holds the length block: E(K, J0), on its lane
+        acc = gmul_group_w(lds, acc, LDS_AES_BYTES, lane_here());  // the group's sum times H (table 0, window-major)
+        if (valid && m_hi * G >= N && j == jl)  // the segment holds the length block: E(K, J0), on its lane
             acc ^= u32x4(*(const lds_u32x4 *)(lds + ekslot));
     }
     // whole record (finish): tag = GHASH ^ E(K, J0), written after the ciphertext (seal) or compared with the

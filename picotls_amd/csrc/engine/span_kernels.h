@@ -18,9 +18,8 @@
 #define SPAN_LDS (LDS_BYTES + GHASH_TABLE_BYTES + 16 * SPAN_MAX_UNITS)  // AES + H^1..H^8 + H^128 tables + partials
 
 // Workgroup s: the units [s * span, min(units, (s + 1) * span)) of the record args.one (key 0 of args.keys), Q_s to
-// part[s]. 16-step units; the record's stream is front-padded to whole steps (gcm_segment, not aligned). CT: the
-// constant-time variant (gcm_segment's uniform-table last multiply; the span's Horner with gmul_tab, every lane the same
-// table rows, instead of the group-cooperative gmul_group whose lanes read different window rows).
+// part[s]. 16-step units; the record's stream is front-padded to whole steps (gcm_segment, not aligned). CT is
+// instantiated true only (the segment end and the span's Horner are conflict-free window-major lookups, ghash.h).
 template <int NR, bool OPEN, bool CT>
 __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGINE_WAVES_PER_SIMD, ENGINE_WAVES_PER_SIMD))) void gcm_span_kernel(BatchArgs args, u32 span, u32 units, u32x4 *part)
 {
@@ -32,8 +31,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
     const u32 wave = threadIdx.x >> 6;
     // AES tables on waves 0..10, H^1..H^8 and H^128 (slot 8) on waves 11..15
     if (wave >= EARLY_GHASH_WAVE)
-        build_ghash_tables(lds, args.keys, 9, 8, 0, EARLY_GHASH_WAVE * 64, ENGINE_WG - EARLY_GHASH_WAVE * 64, false,
-                           GHASH_WMASK(CT));
+        build_ghash_tables(lds, args.keys, 9, 8, 0, EARLY_GHASH_WAVE * 64, ENGINE_WG - EARLY_GHASH_WAVE * 64, GHASH_WMASK);
     else
         build_aes_tables(lds, 0, EARLY_GHASH_WAVE * 64);
     __syncthreads();
@@ -61,8 +59,8 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         }
         u32x4 acc;
         u32 okw;
-        gcm_segment<NR, OPEN, 1, 0, CT>(args, lds, rk, iv0, iv1, iv2, r, valid, m_lo, m_hi, j, laneoff, tsel_horner, acc,
-                                        false, okw, false, LDS_BYTES + GHASH_TABLE_BYTES + 16u * uu);
+        gcm_segment<NR, OPEN, 0, CT>(args, lds, rk, iv0, iv1, iv2, r, valid, m_lo, m_hi, j, laneoff, tsel_horner, acc, false,
+                                     okw, false, LDS_BYTES + GHASH_TABLE_BYTES + 16u * uu);
         if (valid && j == G - 1)  // (the record's last unit includes E(K, J0), gcm_segment)
             s_part[uu] = acc;
     }
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         if (lane < G) {
             u32x4 g = s_part[n - 1];
             for (u32 i = n - 1; i-- > 0;)
-                g = gmul_combine<CT>(lds, g, tsel_chunk, lane) ^ s_part[i];
+                g = gmul_combine(lds, g, tsel_chunk, lane) ^ s_part[i];
             if (j == 0)
                 part[blockIdx.x] = g;
         }

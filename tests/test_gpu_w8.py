@@ -5,7 +5,7 @@ end, w8_tree_end) for whole runs of records of at least W8_MIN_STEPS steps, laun
 (the EXT 4 workgroups tell it which have none). Cases: one key and several, AES-128 and AES-256, the 64-step threshold
 inside one run, seal / open / tamper, in place, and batches mixing long whole runs with short whole runs and cut runs, so
 that both kernels work and skip the other's runs. The reference's per-block GHASH amortisation is lib/fusion.c:515-620
-(six blocks per reduction); the tests hold for any build (with W8_HORNER 0 the same records take the 4-bit path)."""
+(six blocks per reduction)."""
 import os
 
 import numpy as np
@@ -429,8 +429,8 @@ def test_w8_multi_key_runs_vs_fusion(ref, length, aad, key_size, per_key, n):
     (100, 17, 16, 0, "byte"), (4095, 13, 16, 0, "16"), (63, 5, 32, 0, "16"), (1200, 13, 16, 64, "16"),
     (700, 21, 32, 40, "byte")])
 def test_w8_g4_open_into_shifted_outputs_vs_fusion(ref, length, aad, key_size, per_key, shift):
-    """(round 6) A 4-lane group's open aligns its steps to the record's text (G4_OPEN_TEXT_STEPS), so its output is no
-    longer aligned to the steps, and its steady steps hold blocks until a 128-byte line is whole (G4_LINE_HOLD: early
+    """(round 6) A 4-lane group's open aligns its steps to the record's text (segment.h), so its output is no
+    longer aligned to the steps, and its steady steps hold blocks until a 128-byte line is whole (LINE: early
     and late lanes, the range's first and last steps). The plaintexts go to outputs shifted by 16 x (i mod 8) bytes or
     by any byte count, for one key (short whole runs) and for connections of 40-64 records (MK runs), with AADs of
     0-3 blocks (text block 0 at every position of a step); every byte of the output buffer, tags and ok bytes against
