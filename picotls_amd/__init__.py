@@ -11,6 +11,9 @@ operator interface (``include/picotls.h:519-580, 2082-2164``; ``lib/picotls.c:65
 * :class:`Keyset`, :func:`seal_batch`, :func:`open_batch`, :func:`ecb_batch`, :func:`hp_mask_batch`,
   :func:`seal_batch_hp`, :func:`quiclb_batch` -- the batch extension.
 * :class:`QuicLbCipher` -- mirror of ``ptls_mi355x_quiclb`` (fusion's ``ptls_fusion_quiclb``).
+* :class:`ChaChaKeyset`, :func:`chacha_seal_batch`, :func:`chacha_open_batch`, :func:`chacha_seal_tls_records`,
+  :func:`chacha_open_tls_records`, :func:`chacha_hp_mask_batch`, :data:`chacha20poly1305`, :class:`ChaChaCipher` -- the
+  ChaCha20-Poly1305 engine of ``include/picotls/mi355x_chacha20.h`` (``ptls_mi355x_chacha20poly1305`` / ``_chacha20``).
 
 There is no CPU fallback: when the shared object or a gfx950 device is missing every entry point raises.
 """
@@ -74,6 +77,29 @@ DEBUG_FUNCTIONS = (
     "ptls_mi355x_debug_wallclock_khz",
     "ptls_mi355x_debug_kernel_clock",
     "ptls_mi355x_debug_kernel_clock_count",
+)
+
+# every function of include/picotls/mi355x_chacha20.h: the ChaCha20-Poly1305 engine (same shared object)
+CHACHA_ABI_FUNCTIONS = (
+    "ptls_mi355x_chacha_keyset_new",
+    "ptls_mi355x_chacha_keyset_free",
+    "ptls_mi355x_chacha_keyset_size",
+    "ptls_mi355x_chacha_keyset_device",
+    "ptls_mi355x_chacha_keyset_update",
+    "ptls_mi355x_chacha_keyset_get_iv",
+    "ptls_mi355x_chacha_keyset_set_iv",
+    "ptls_mi355x_chacha_seal_batch",
+    "ptls_mi355x_chacha_open_batch",
+    "ptls_mi355x_chacha_seal_tls_records",
+    "ptls_mi355x_chacha_open_tls_records",
+    "ptls_mi355x_chacha_hp_mask_batch",
+    "ptls_mi355x_chacha_encrypt",
+    "ptls_mi355x_chacha_encrypt_v",
+    "ptls_mi355x_chacha_decrypt",
+    "ptls_mi355x_chacha_hp_mask",
+    "ptls_mi355x_chacha_debug_poly1305",
+    "ptls_mi355x_chacha_debug_force",
+    "ptls_mi355x_chacha_debug_counters",
 )
 
 SIZE_MAX = ctypes.c_size_t(-1).value
@@ -144,6 +170,30 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.ptls_mi355x_debug_wallclock_khz.restype = ci
     lib.ptls_mi355x_debug_kernel_clock.argtypes = [vp, ctypes.c_uint]
     lib.ptls_mi355x_debug_kernel_clock_count.restype = ci
+    lib.ptls_mi355x_chacha_keyset_new.argtypes = [vp, vp, sz]
+    lib.ptls_mi355x_chacha_keyset_new.restype = vp
+    lib.ptls_mi355x_chacha_keyset_free.argtypes = [vp]
+    lib.ptls_mi355x_chacha_keyset_free.restype = None
+    lib.ptls_mi355x_chacha_keyset_size.argtypes = [vp]
+    lib.ptls_mi355x_chacha_keyset_size.restype = sz
+    lib.ptls_mi355x_chacha_keyset_device.argtypes = [vp]
+    lib.ptls_mi355x_chacha_keyset_device.restype = ci
+    lib.ptls_mi355x_chacha_keyset_update.argtypes = [vp, vp, vp, vp, sz]
+    lib.ptls_mi355x_chacha_keyset_get_iv.argtypes = [vp, sz, vp]
+    lib.ptls_mi355x_chacha_keyset_set_iv.argtypes = [vp, sz, vp]
+    lib.ptls_mi355x_chacha_seal_batch.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    lib.ptls_mi355x_chacha_open_batch.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.ptls_mi355x_chacha_seal_tls_records.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.ptls_mi355x_chacha_open_tls_records.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    lib.ptls_mi355x_chacha_hp_mask_batch.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.ptls_mi355x_chacha_encrypt.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
+    lib.ptls_mi355x_chacha_encrypt_v.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
+    lib.ptls_mi355x_chacha_decrypt.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
+    lib.ptls_mi355x_chacha_decrypt.restype = sz
+    lib.ptls_mi355x_chacha_hp_mask.argtypes = [vp, sz, vp, vp]
+    lib.ptls_mi355x_chacha_debug_poly1305.argtypes = [vp, vp, sz, vp]
+    lib.ptls_mi355x_chacha_debug_force.argtypes = [ci, ci]
+    lib.ptls_mi355x_chacha_debug_counters.argtypes = [vp, ci]
     _lib = lib
     return lib
 
@@ -316,6 +366,123 @@ def quiclb_batch(ks: Keyset, cids_ptr: int, n: int, in_ptr: int, out_ptr: int, s
         raise _err("ptls_mi355x_quiclb_batch")
 
 
+# ------------------------------------------------------------------------------------------------ ChaCha20-Poly1305
+
+
+class ChaChaKeyset:
+    """N ChaCha20-Poly1305 traffic keys (32-byte key, 12-byte static IV) resident on the current device
+    (ptls_mi355x_chacha_keyset_new). Sizes are checked before anything touches a device."""
+
+    key_size = 32
+
+    def __init__(self, keys: bytes | np.ndarray, ivs: bytes | np.ndarray):
+        keys = np.frombuffer(bytes(keys), dtype=np.uint8) if not isinstance(keys, np.ndarray) else np.ascontiguousarray(keys, np.uint8)
+        ivs = np.frombuffer(bytes(ivs), dtype=np.uint8) if not isinstance(ivs, np.ndarray) else np.ascontiguousarray(ivs, np.uint8)
+        if keys.size == 0 or keys.size % 32 or ivs.size != keys.size // 32 * 12:
+            raise ValueError("keys must be n*32 bytes and ivs n*12 bytes")
+        lib = load_library()
+        self.n = keys.size // 32
+        h = lib.ptls_mi355x_chacha_keyset_new(_buf(keys), _buf(ivs), self.n)
+        if not h:
+            raise _err("ptls_mi355x_chacha_keyset_new")
+        self.handle = ctypes.c_void_p(h)
+
+    def free(self):
+        if getattr(self, "handle", None):
+            load_library().ptls_mi355x_chacha_keyset_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def get_iv(self, idx: int = 0) -> bytes:
+        out = bytearray(12)
+        if load_library().ptls_mi355x_chacha_keyset_get_iv(self.handle, idx, _buf(out)) != 0:
+            raise _err("chacha get_iv")
+        return bytes(out)
+
+    def set_iv(self, iv: bytes, idx: int = 0) -> None:
+        if len(iv) != 12:
+            raise ValueError("the static IV is 12 bytes")
+        if load_library().ptls_mi355x_chacha_keyset_set_iv(self.handle, idx, _buf(bytes(iv))) != 0:
+            raise _err("chacha set_iv")
+
+    def update(self, key_idx, keys: bytes, ivs: bytes) -> None:
+        """Rekeys entries key_idx (ptls_mi355x_chacha_keyset_update), stream-ordered like Keyset.update."""
+        idx = np.ascontiguousarray(key_idx, dtype=np.uint32)
+        k = np.frombuffer(bytes(keys), np.uint8)
+        v = np.frombuffer(bytes(ivs), np.uint8)
+        if k.size != idx.size * 32 or v.size != idx.size * 12:
+            raise ValueError("keys must be n*32 bytes and ivs n*12 bytes")
+        if load_library().ptls_mi355x_chacha_keyset_update(self.handle, _buf(idx), _buf(k), _buf(v), idx.size) != 0:
+            raise _err("chacha keyset_update")
+
+
+def chacha_seal_batch(ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, aad_ptr: int, out_ptr: int, stream: int = 0) -> None:
+    """seal_batch under ChaCha20-Poly1305: device pointers, asynchronous on ``stream``."""
+    if load_library().ptls_mi355x_chacha_seal_batch(ks.handle, recs_ptr, nrecs, in_ptr, aad_ptr or None, out_ptr, stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_seal_batch")
+
+
+def chacha_open_batch(ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, aad_ptr: int, out_ptr: int, ok_ptr: int,
+                      stream: int = 0) -> None:
+    """open_batch under ChaCha20-Poly1305. A record whose tag fails reports ok = 0; its bytes in ``out`` may have been
+    written and must not be used."""
+    if load_library().ptls_mi355x_chacha_open_batch(ks.handle, recs_ptr, nrecs, in_ptr, aad_ptr or None, out_ptr, ok_ptr,
+                                                    stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_open_batch")
+
+
+def chacha_seal_tls_records(ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, stream: int = 0) -> None:
+    """TLS 1.3 wire records under ChaCha20-Poly1305 (layout of seal_tls_records); device pointers."""
+    if load_library().ptls_mi355x_chacha_seal_tls_records(ks.handle, recs_ptr, nrecs, in_ptr, out_ptr, stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_seal_tls_records")
+
+
+def chacha_open_tls_records(ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, ok_ptr: int,
+                            results_ptr: int = 0, stream: int = 0) -> None:
+    """Opens TLS 1.3 wire records under ChaCha20-Poly1305 (TLS_RESULT_DTYPE results); device pointers."""
+    if load_library().ptls_mi355x_chacha_open_tls_records(ks.handle, recs_ptr, nrecs, in_ptr, out_ptr, ok_ptr,
+                                                          results_ptr or None, stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_open_tls_records")
+
+
+def chacha_hp_mask_batch(hp_ks: ChaChaKeyset, hp_ptr: int, n: int, base_ptr: int, masks_ptr: int, stream: int = 0) -> None:
+    """QUIC header-protection masks of the ChaCha20 suites (HP_DTYPE entries, 16 bytes per mask); device pointers."""
+    if load_library().ptls_mi355x_chacha_hp_mask_batch(hp_ks.handle, hp_ptr, n, base_ptr, masks_ptr, stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_hp_mask_batch")
+
+
+def chacha_debug_poly1305(key32: bytes, msg: bytes) -> bytes:
+    """The device Poly1305 routine on a given one-time key (ptls_mi355x_chacha_debug_poly1305)."""
+    if len(key32) != 32:
+        raise ValueError("the one-time key is 32 bytes")
+    tag = bytearray(16)
+    if load_library().ptls_mi355x_chacha_debug_poly1305(_buf(bytes(key32)), _buf(bytes(msg)), len(msg), _buf(tag)) != 0:
+        raise _err("ptls_mi355x_chacha_debug_poly1305")
+    return bytes(tag)
+
+
+CHACHA_GROUP_WIDTHS = (4, 16)  # lanes per record of the compiled seal / open variants
+
+
+def chacha_debug_force(group_lanes: int = 0, max_workgroups: int = 0) -> None:
+    """0, 0 = automatic; otherwise the group width (one of CHACHA_GROUP_WIDTHS) and a cap on the launch grid."""
+    if load_library().ptls_mi355x_chacha_debug_force(group_lanes, max_workgroups) != 0:
+        raise _err("ptls_mi355x_chacha_debug_force")
+
+
+def chacha_debug_counters(reset: bool = False) -> dict:
+    """Launches per group width since the last reset: {4: n, 16: n}. Waits for the device."""
+    out = (ctypes.c_uint64 * 2)()
+    if load_library().ptls_mi355x_chacha_debug_counters(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0) != 0:
+        raise _err("ptls_mi355x_chacha_debug_counters")
+    return dict(zip(CHACHA_GROUP_WIDTHS, (int(out[0]), int(out[1]))))
+
+
 # ------------------------------------------------------------------------------------------------ picotls mirror
 
 
@@ -337,6 +504,9 @@ class AeadAlgorithm:
 
 aes128gcm = AeadAlgorithm("AES128-GCM", 16)
 aes256gcm = AeadAlgorithm("AES256-GCM", 32)
+# ptls_mi355x_chacha20poly1305 (PTLS_CHACHA20POLY1305_* limits, include/picotls.h:98-99; TLS 1.2 IV sizes {12, 0})
+chacha20poly1305 = AeadAlgorithm("CHACHA20-POLY1305", 32, confidentiality_limit=2**64 - 1, integrity_limit=2**36,
+                                 tls12_fixed_iv_size=12)
 
 
 class AeadContext:
@@ -348,6 +518,11 @@ class AeadContext:
         self.algo = algo
         self.is_enc = is_enc
         self._iv = bytes(iv)
+        self._pfx = "ptls_mi355x_"  # the per-record calls of the algorithm's engine
+        if algo.name == "CHACHA20-POLY1305":
+            self._pfx = "ptls_mi355x_chacha_"
+            self.ks = ChaChaKeyset(key, iv)
+            return
         self.ks = Keyset(key, iv, algo.key_size)
         # as the picotls objects (ptls_mi355x.c aesgcm_setup): constant-time unless PTLS_MI355X_CONSTANT_TIME=0
         self.ks.set_constant_time(os.environ.get("PTLS_MI355X_CONSTANT_TIME") != "0")
@@ -372,9 +547,9 @@ class AeadContext:
     # ptls_aead_encrypt (include/picotls.h:2102-2107): returns ciphertext || tag
     def encrypt(self, pt: bytes, seq: int, aad: bytes = b"") -> bytes:
         out = bytearray(len(pt) + self.algo.tag_size)
-        if load_library().ptls_mi355x_encrypt(self.ks.handle, 0, _buf(out), _buf(bytes(pt)), len(pt), seq,
-                                             _buf(bytes(aad)), len(aad)) != 0:
-            raise _err("ptls_mi355x_encrypt")
+        if getattr(load_library(), self._pfx + "encrypt")(self.ks.handle, 0, _buf(out), _buf(bytes(pt)), len(pt), seq,
+                                                           _buf(bytes(aad)), len(aad)) != 0:
+            raise _err(self._pfx + "encrypt")
         return bytes(out)
 
     # ptls_aead_encrypt_v (include/picotls.h:2115-2119): the vectors sealed as one record
@@ -386,9 +561,9 @@ class AeadContext:
             arr[2 * i + 1] = len(b)
         total = sum(len(b) for b in bufs)
         out = bytearray(total + self.algo.tag_size)
-        if load_library().ptls_mi355x_encrypt_v(self.ks.handle, 0, _buf(out), ctypes.cast(arr, ctypes.c_void_p), len(bufs), seq,
-                                               _buf(bytes(aad)), len(aad)) != 0:
-            raise _err("ptls_mi355x_encrypt_v")
+        if getattr(load_library(), self._pfx + "encrypt_v")(self.ks.handle, 0, _buf(out), ctypes.cast(arr, ctypes.c_void_p),
+                                                             len(bufs), seq, _buf(bytes(aad)), len(aad)) != 0:
+            raise _err(self._pfx + "encrypt_v")
         return bytes(out)
 
     # ptls_aead_encrypt_s with a header-protection cipher (include/picotls.h:2109-2113, lib/fusion.c:425-430,636-651):
@@ -402,12 +577,16 @@ class AeadContext:
         return bytes(out), bytes(mask)
 
     # ptls_aead_decrypt (include/picotls.h:2160-2164): plaintext, or None for SIZE_MAX
-    def decrypt(self, ct_tag: bytes, seq: int, aad: bytes = b"") -> bytes | None:
+    def decrypt(self, ct_tag: bytes, seq: int, aad: bytes = b"", out: bytearray | None = None) -> bytes | None:
+        """``out`` (optional, at least len(ct_tag) - 16 bytes): the buffer the engine writes the plaintext to."""
         if len(ct_tag) < 16:
             return None
-        out = bytearray(len(ct_tag) - 16 + 1)
-        r = load_library().ptls_mi355x_decrypt(self.ks.handle, 0, _buf(out), _buf(bytes(ct_tag)), len(ct_tag), seq,
-                                               _buf(bytes(aad)), len(aad))
+        if out is None:
+            out = bytearray(len(ct_tag) - 16 + 1)
+        elif len(out) < len(ct_tag) - 16:
+            raise ValueError("output buffer too small")
+        r = getattr(load_library(), self._pfx + "decrypt")(self.ks.handle, 0, _buf(out), _buf(bytes(ct_tag)), len(ct_tag), seq,
+                                                           _buf(bytes(aad)), len(aad))
         if r == SIZE_MAX:
             return None
         return bytes(out[:r])
@@ -423,6 +602,22 @@ class CtrCipher:
         out = bytearray(16)
         if load_library().ptls_mi355x_encrypt_block(self.ks.handle, 0, _buf(out), _buf(bytes(iv16))) != 0:
             raise _err("ptls_mi355x_encrypt_block")
+        return bytes(out)
+
+
+class ChaChaCipher:
+    """Mirror of ptls_mi355x_chacha20 as QUIC header protection uses it: ptls_cipher_init with the 16-byte IV (block counter
+    || nonce), then the first 16 keystream bytes."""
+
+    def __init__(self, key: bytes):
+        self.ks = ChaChaKeyset(key, bytes(12))
+
+    def mask(self, iv16: bytes) -> bytes:
+        if len(iv16) != 16:
+            raise ValueError("the ChaCha20 IV is 16 bytes")
+        out = bytearray(16)
+        if load_library().ptls_mi355x_chacha_hp_mask(self.ks.handle, 0, _buf(out), _buf(bytes(iv16))) != 0:
+            raise _err("ptls_mi355x_chacha_hp_mask")
         return bytes(out)
 
 

@@ -23,10 +23,12 @@ PICOTLS_INCLUDE = os.environ.get("PICOTLS_INCLUDE", "/root/reference/include")
 # occupancy-driven one (+5 % seal+open on 16 KiB and 1200 B records, interleaved A/B with tools/ab.py).
 ENGINE_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 ENGINE_SRCS = [os.path.join(PKG, "csrc", "aesgcm_engine.hip")]
-PICOTLS_SRCS = [os.path.join(PKG, "csrc", "ptls_mi355x.c")]
-HEADERS = [os.path.join(ROOT, "include", "picotls", h) for h in ("mi355x.h", "mi355x_picotls.h", "mi355x_debug.h")]
-ENGINE_PARTS = sorted(os.path.join(PKG, "csrc", "engine", f) for f in os.listdir(os.path.join(PKG, "csrc", "engine"))
-                      if f.endswith(".h"))  # included by aesgcm_engine.hip (one translation unit)
+PICOTLS_SRCS = [os.path.join(PKG, "csrc", "ptls_mi355x.c"), os.path.join(PKG, "csrc", "ptls_mi355x_chacha20.c")]
+HEADERS = [os.path.join(ROOT, "include", "picotls", h) for h in ("mi355x.h", "mi355x_picotls.h", "mi355x_debug.h",
+                                                                  "mi355x_chacha20.h", "mi355x_chacha20_picotls.h")]
+# included by aesgcm_engine.hip (one translation unit): the AES-GCM engine's parts and the ChaCha20-Poly1305 ones
+ENGINE_PARTS = sorted(os.path.join(PKG, "csrc", d, f) for d in ("engine", "chacha")
+                      for f in os.listdir(os.path.join(PKG, "csrc", d)) if f.endswith(".h"))
 
 
 def source_digest(files: list[str], extra: str = "") -> str:

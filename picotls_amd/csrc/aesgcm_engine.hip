@@ -2081,3 +2081,12 @@ int ptls_mi355x_encrypt_block(ptls_mi355x_keyset_t *ks, size_t key_idx, void *ou
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ ChaCha20-Poly1305
+// The second AEAD family (include/picotls/mi355x_chacha20.h), in this translation unit so that its host side shares the
+// per-device state, streams and staging pool above. Nothing above depends on it.
+#include "picotls/mi355x_chacha20.h"
+#include "chacha/chacha20.h"
+#include "chacha/poly1305.h"
+#include "chacha/kernels.h"
+#include "chacha/host.h"

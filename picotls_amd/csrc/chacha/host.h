@@ -1,0 +1,496 @@
+// picotls_amd/csrc/chacha/host.h -- host side of the ChaCha20-Poly1305 engine: the C ABI of
+// include/picotls/mi355x_chacha20.h. Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip, included
+// last: it uses that file's per-device state, streams, event pool, staging pool (StageCall) and error reporting.
+#ifndef PTLS_MI355X_CHACHA_HOST_H
+#define PTLS_MI355X_CHACHA_HOST_H
+
+#define CHACHA_WG_PER_CU 4    // launch grid: this many 256-thread workgroups per CU at most (what ~120 VGPRs a lane keep resident)
+#define CHACHA_CLAIM_SLOTS 8  // claim counters per keyset: one per stream in use, shared in stream order beyond that
+
+// A keyset is the entry array and, behind it, its claim counters (a pair of u64 per slot, zero between launches).
+// Launches on one stream run in order and share a slot; a stream without one takes a free slot, or takes a slot over
+// after waiting for its last launch.
+struct st_ptls_mi355x_chacha_keyset_t {
+    DeviceState *ds = nullptr;
+    int device = 0;
+    size_t nkeys = 0;
+    ChaChaKey *d_keys = nullptr;
+    unsigned long long *d_claim = nullptr;
+    std::vector<uint8_t> ivs;  // the static IVs (get_iv reads these; the device copy is what seals use)
+    std::mutex mu;             // launches from several threads: the slots below
+    std::vector<std::pair<hipStream_t, hipEvent_t>> uses;  // slot i: its stream, and the event after its last launch
+    unsigned takeover = 0;
+};
+
+static std::atomic<u32> g_chacha_force_g{0}, g_chacha_force_wgs{0};
+
+// the claim slot of `s` (ks->mu held); a slot taken over from another stream is first waited for
+static int chacha_slot_locked(ptls_mi355x_chacha_keyset_t *ks, hipStream_t s)
+{
+    for (size_t i = 0; i < ks->uses.size(); ++i)
+        if (ks->uses[i].first == s)
+            return (int)i;
+    if (ks->uses.size() < CHACHA_CLAIM_SLOTS) {
+        hipEvent_t e = event_get(ks->ds);
+        if (e == nullptr)
+            return fail("%s", "event creation failed");
+        ks->uses.emplace_back(s, e);
+        return (int)ks->uses.size() - 1;
+    }
+    const int i = (int)(ks->takeover++ % CHACHA_CLAIM_SLOTS);
+    HIP_TRY(hipStreamWaitEvent(s, ks->uses[i].second, 0));
+    ks->uses[i].first = s;
+    return i;
+}
+
+// orders the maintenance stream after every launch that used the keyset
+static int chacha_maint_after_uses(ptls_mi355x_chacha_keyset_t *ks)
+{
+    std::lock_guard<std::mutex> lk(ks->mu);
+    for (auto &u : ks->uses)
+        HIP_TRY(hipStreamWaitEvent(ks->ds->maint, u.second, 0));
+    return 0;
+}
+
+static unsigned chacha_grid(const DeviceState *ds, size_t nrecs)
+{
+    u64 grid = (nrecs + CHACHA_WG / CHACHA_G_WIDE - 1) / (CHACHA_WG / CHACHA_G_WIDE);
+    grid = min(grid, (u64)ds->ncu * CHACHA_WG_PER_CU);
+    const u32 cap = g_chacha_force_wgs.load(std::memory_order_relaxed);
+    if (cap != 0)
+        grid = min(grid, (u64)cap);
+    return (unsigned)grid;
+}
+
+static void chacha_launch_kernel(bool open, int frame, unsigned grid, hipStream_t s, const ChaChaArgs &a)
+{
+    if (frame == 0) {
+        if (open)
+            chacha_batch_kernel<true, 0><<<grid, CHACHA_WG, 0, s>>>(a);
+        else
+            chacha_batch_kernel<false, 0><<<grid, CHACHA_WG, 0, s>>>(a);
+    } else {
+        if (open)
+            chacha_batch_kernel<true, 1><<<grid, CHACHA_WG, 0, s>>>(a);
+        else
+            chacha_batch_kernel<false, 1><<<grid, CHACHA_WG, 0, s>>>(a);
+    }
+}
+
+static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int frame, const ptls_mi355x_record_t *recs, size_t nrecs,
+                               const void *in, const void *aad, void *out, uint8_t *ok, void *stream)
+{
+    if (ks == NULL || (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && ok == NULL))))
+        return fail("%s", "chacha batch: invalid arguments");
+    if (nrecs == 0)
+        return 0;
+    DeviceScope scope(ks->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(ks->mu);
+    const int slot = chacha_slot_locked(ks, s);
+    if (slot < 0)
+        return -1;
+    ChaChaArgs a = {};
+    a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
+    a.recs = recs, a.nrecs = nrecs, a.in = (const uint8_t *)in, a.aad = (const uint8_t *)aad, a.out = (uint8_t *)out, a.ok = ok;
+    a.claim = ks->d_claim + 2 * slot;
+    LAUNCH_CLEAR();
+    chacha_launch_kernel(open, frame, chacha_grid(ks->ds, nrecs), s, a);
+    const hipError_t e = hipGetLastError();
+    // (the use is recorded either way: teardown and a takeover of the slot wait for whatever was queued)
+    const hipError_t rec = hipEventRecord(ks->uses[slot].second, s);
+    if (e != hipSuccess)
+        return fail("chacha batch launch: %s", hipGetErrorString(e));
+    return rec == hipSuccess ? 0 : fail("%s", "hipEventRecord failed");
+}
+
+extern "C" {
+
+ptls_mi355x_chacha_keyset_t *ptls_mi355x_chacha_keyset_new(const void *keys, const void *ivs, size_t nkeys)
+{
+    if (keys == NULL || ivs == NULL || nkeys == 0 || nkeys > (1u << 30)) {
+        fail("%s", "ptls_mi355x_chacha_keyset_new: invalid arguments");
+        return NULL;
+    }
+    DeviceState *ds = current_device_state();
+    if (ds == nullptr)
+        return NULL;
+    ptls_mi355x_chacha_keyset_t *ks = new (std::nothrow) st_ptls_mi355x_chacha_keyset_t();
+    if (ks == nullptr) {
+        fail("%s", "out of memory");
+        return NULL;
+    }
+    ks->ds = ds, ks->device = ds->device, ks->nkeys = nkeys;
+    ks->ivs.assign((const uint8_t *)ivs, (const uint8_t *)ivs + nkeys * 12);
+    std::vector<ChaChaKey> host(nkeys);
+    for (size_t i = 0; i < nkeys; ++i) {
+        memset(&host[i], 0, sizeof(ChaChaKey));
+        memcpy(host[i].key, (const uint8_t *)keys + i * 32, 32);
+        memcpy(host[i].iv, (const uint8_t *)ivs + i * 12, 12);
+    }
+    // entries and counters in stream-ordered memory on the setup stream; the call waits for that stream only
+    const size_t kbytes = nkeys * sizeof(ChaChaKey), cbytes = CHACHA_CLAIM_SLOTS * 2 * sizeof(unsigned long long);
+    const bool ok = hipMallocAsync((void **)&ks->d_keys, kbytes + cbytes, ds->setup) == hipSuccess &&
+                    hipMemcpyAsync(ks->d_keys, host.data(), kbytes, hipMemcpyHostToDevice, ds->setup) == hipSuccess &&
+                    hipMemsetAsync((uint8_t *)ks->d_keys + kbytes, 0, cbytes, ds->setup) == hipSuccess &&
+                    hipStreamSynchronize(ds->setup) == hipSuccess;
+    clear_memory(host.data(), kbytes);
+    if (!ok) {
+        (void)hipGetLastError();
+        if (ks->d_keys != nullptr)
+            (void)hipFreeAsync(ks->d_keys, ds->setup);
+        clear_memory(ks->ivs.data(), ks->ivs.size());
+        delete ks;
+        fail("%s", "ptls_mi355x_chacha_keyset_new: device setup failed");
+        return NULL;
+    }
+    ks->d_claim = (unsigned long long *)((uint8_t *)ks->d_keys + kbytes);
+    return ks;
+}
+
+void ptls_mi355x_chacha_keyset_free(ptls_mi355x_chacha_keyset_t *ks)
+{
+    if (ks == NULL)
+        return;
+    DeviceScope scope(ks->device);
+    DeviceState *ds = ks->ds;
+    // the key material is cleared after the keyset's last launch, on the maintenance stream; where that order cannot be
+    // set up on the device the host waits for the launches instead, and failing that too the entries are left as they are
+    bool ordered = chacha_maint_after_uses(ks) == 0;
+    if (!ordered) {
+        ordered = true;
+        for (auto &u : ks->uses)
+            ordered = hipEventSynchronize(u.second) == hipSuccess && ordered;
+    }
+    if (ordered) {
+        (void)hipMemsetAsync(ks->d_keys, 0, ks->nkeys * sizeof(ChaChaKey), ds->maint);
+        (void)hipFreeAsync(ks->d_keys, ds->maint);
+    }
+    for (auto &u : ks->uses)
+        event_put(ds, u.second);
+    clear_memory(ks->ivs.data(), ks->ivs.size());
+    delete ks;
+}
+
+size_t ptls_mi355x_chacha_keyset_size(const ptls_mi355x_chacha_keyset_t *ks) { return ks->nkeys; }
+int ptls_mi355x_chacha_keyset_device(const ptls_mi355x_chacha_keyset_t *ks) { return ks->device; }
+
+int ptls_mi355x_chacha_keyset_update(ptls_mi355x_chacha_keyset_t *ks, const uint32_t *key_idx, const void *keys, const void *ivs,
+                                     size_t n)
+{
+    if (ks == NULL || (n != 0 && (key_idx == NULL || keys == NULL || ivs == NULL)))
+        return fail("%s", "chacha keyset_update: invalid arguments");
+    std::vector<bool> seen(n != 0 ? ks->nkeys : 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (key_idx[i] >= ks->nkeys)
+            return fail("%s", "chacha keyset_update: key index out of range");
+        if (seen[key_idx[i]])
+            return fail("%s", "chacha keyset_update: key index listed twice");
+        seen[key_idx[i]] = true;
+    }
+    if (n == 0)
+        return 0;
+    DeviceScope scope(ks->device);
+    DeviceState *ds = ks->ds;
+    std::vector<ChaChaKey> host(n);
+    for (size_t i = 0; i < n; ++i) {
+        memset(&host[i], 0, sizeof(ChaChaKey));
+        memcpy(host[i].key, (const uint8_t *)keys + i * 32, 32);
+        memcpy(host[i].iv, (const uint8_t *)ivs + i * 12, 12);
+    }
+    // on the maintenance stream, after every launch already made with the old entries; the call returns once the
+    // scatter has run, so launches made after it see the new ones
+    if (chacha_maint_after_uses(ks) != 0)
+        return -1;
+    uint8_t *d = NULL;
+    const size_t kb = n * sizeof(ChaChaKey), sb = n * 4;
+    HIP_TRY(hipMallocAsync((void **)&d, kb + sb, ds->maint));
+    int ret = -1;
+    if (hipMemcpyAsync(d, host.data(), kb, hipMemcpyHostToDevice, ds->maint) == hipSuccess &&
+        hipMemcpyAsync(d + kb, key_idx, sb, hipMemcpyHostToDevice, ds->maint) == hipSuccess) {
+        LAUNCH_CLEAR();
+        chacha_keys_scatter_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ds->maint>>>((const ChaChaKey *)d, (const u32 *)(d + kb),
+                                                                                      ks->d_keys, (u32)n);
+        if (hipGetLastError() == hipSuccess)
+            ret = 0;
+    }
+    (void)hipMemsetAsync(d, 0, kb, ds->maint);
+    (void)hipFreeAsync(d, ds->maint);
+    if (hipStreamSynchronize(ds->maint) != hipSuccess)
+        ret = -1;
+    clear_memory(host.data(), kb);
+    if (ret != 0)
+        return fail("%s", "chacha keyset_update: device update failed");
+    for (size_t i = 0; i < n; ++i)
+        memcpy(ks->ivs.data() + (size_t)key_idx[i] * 12, (const uint8_t *)ivs + i * 12, 12);
+    return 0;
+}
+
+int ptls_mi355x_chacha_keyset_get_iv(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, void *iv)
+{
+    if (ks == NULL || key_idx >= ks->nkeys || iv == NULL)
+        return fail("%s", "chacha get_iv: bad key index");
+    memcpy(iv, ks->ivs.data() + key_idx * 12, 12);
+    return 0;
+}
+
+int ptls_mi355x_chacha_keyset_set_iv(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, const void *iv)
+{
+    if (ks == NULL || key_idx >= ks->nkeys || iv == NULL)
+        return fail("%s", "chacha set_iv: bad key index");
+    DeviceScope scope(ks->device);
+    if (chacha_maint_after_uses(ks) != 0)
+        return -1;
+    HIP_TRY(hipMemcpyAsync(ks->d_keys[key_idx].iv, iv, 12, hipMemcpyHostToDevice, ks->ds->maint));
+    HIP_TRY(hipStreamSynchronize(ks->ds->maint));
+    memcpy(ks->ivs.data() + key_idx * 12, iv, 12);
+    return 0;
+}
+
+int ptls_mi355x_chacha_seal_batch(ptls_mi355x_chacha_keyset_t *ks, const ptls_mi355x_record_t *recs, size_t nrecs, const void *in,
+                                  const void *aad, void *out, void *stream)
+{
+    return chacha_launch_batch(ks, false, 0, recs, nrecs, in, aad, out, NULL, stream);
+}
+
+int ptls_mi355x_chacha_open_batch(ptls_mi355x_chacha_keyset_t *ks, const ptls_mi355x_record_t *recs, size_t nrecs, const void *in,
+                                  const void *aad, void *out, uint8_t *ok, void *stream)
+{
+    return chacha_launch_batch(ks, true, 0, recs, nrecs, in, aad, out, ok, stream);
+}
+
+int ptls_mi355x_chacha_seal_tls_records(ptls_mi355x_chacha_keyset_t *ks, const ptls_mi355x_record_t *recs, size_t nrecs,
+                                        const void *in, void *out, void *stream)
+{
+    return chacha_launch_batch(ks, false, 1, recs, nrecs, in, NULL, out, NULL, stream);
+}
+
+int ptls_mi355x_chacha_open_tls_records(ptls_mi355x_chacha_keyset_t *ks, const ptls_mi355x_record_t *recs, size_t nrecs,
+                                        const void *in, void *out, uint8_t *ok, ptls_mi355x_tls_result_t *results, void *stream)
+{
+    if (chacha_launch_batch(ks, true, 1, recs, nrecs, in, NULL, out, ok, stream) != 0)
+        return -1;
+    if (nrecs == 0)
+        return 0;
+    DeviceScope scope(ks->device);
+    LAUNCH_CLEAR();
+    // header check and padding strip: the same pass as after an AES-GCM open
+    tls_unpad_kernel<<<aux_grid(nrecs, ks->ds->ncu), 256, 0, (hipStream_t)stream>>>(recs, nrecs, (const uint8_t *)in,
+                                                                                     (const uint8_t *)out, ok, results);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int ptls_mi355x_chacha_hp_mask_batch(ptls_mi355x_chacha_keyset_t *hp_ks, const ptls_mi355x_hp_t *hp, size_t n, const void *base,
+                                     void *masks, void *stream)
+{
+    if (hp_ks == NULL || (n != 0 && (hp == NULL || base == NULL || masks == NULL)))
+        return fail("%s", "chacha hp_mask: invalid arguments");
+    if (n == 0)
+        return 0;
+    DeviceScope scope(hp_ks->device);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(hp_ks->mu);
+    const int slot = chacha_slot_locked(hp_ks, s);  // (for its use event: teardown and rekey wait for this launch)
+    if (slot < 0)
+        return -1;
+    LAUNCH_CLEAR();
+    chacha_hp_kernel<<<aux_grid(n, hp_ks->ds->ncu), 256, 0, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, hp, (const uint8_t *)base,
+                                                                 (uint8_t *)masks, n, nullptr, 0);
+    const hipError_t e = hipGetLastError();
+    const hipError_t rec = hipEventRecord(hp_ks->uses[slot].second, s);
+    if (e != hipSuccess)
+        return fail("chacha hp_mask launch: %s", hipGetErrorString(e));
+    return rec == hipSuccess ? 0 : fail("%s", "hipEventRecord failed");
+}
+
+}  // extern "C"
+
+// one record on host buffers: staged, sealed or opened by one launch of one workgroup on the stager's stream, copied back
+static int chacha_single(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, bool open, void *output, const ptls_mi355x_iovec_t *vec,
+                         size_t incnt, size_t len, uint64_t seq, const void *aad, size_t aadlen, int *verified)
+{
+    if (ks == NULL || key_idx >= ks->nkeys || (aadlen != 0 && aad == NULL) || (len != 0 && output == NULL))
+        return fail("%s", "chacha single: invalid arguments");
+    if (len > PTLS_MI355X_MAX_RECORD_LEN || aadlen > PTLS_MI355X_MAX_AAD_LEN)
+        return fail("%s", "chacha single: record or AAD longer than PTLS_MI355X_MAX_RECORD_LEN / PTLS_MI355X_MAX_AAD_LEN");
+    DeviceScope scope(ks->device);
+    StageCall call(ks->ds);
+    // staging: [0, 40) descriptor | AAD | input (open: with the tag) || output (seal: with the tag) | ok byte | done word
+    const size_t aad_at = 64, in_at = aad_at + ((aadlen + 63) & ~(size_t)63), in_len = len + (open ? 16 : 0);
+    const size_t out_at = in_at + ((in_len + 63) & ~(size_t)63), out_len = len + (open ? 0 : 16);
+    const size_t ok_at = out_at + ((out_len + 63) & ~(size_t)63), flag_at = ok_at + 16;
+    if (call.acquire(flag_at + 16) != 0)
+        return -1;
+    uint8_t *h = call.host();
+    ptls_mi355x_record_t rec = {};
+    rec.in_off = in_at, rec.out_off = out_at, rec.seq = seq, rec.aad_off = (u32)aad_at, rec.len = (u32)len;
+    rec.key_idx = (u32)key_idx, rec.aad_len = (uint16_t)aadlen, rec.flags = (uint16_t)(aadlen >> 16);
+    memcpy(h, &rec, sizeof(rec));
+    if (aadlen != 0)
+        memcpy(h + aad_at, aad, aadlen);
+    size_t at = in_at;
+    for (size_t i = 0; i < incnt; ++i) {
+        if (vec[i].len != 0)
+            memcpy(h + at, vec[i].base, vec[i].len);
+        at += vec[i].len;
+    }
+    h[ok_at] = 0;
+    memset(h + flag_at, 0, 4);
+    call.clear_lo = in_at, call.clear_hi = ok_at;
+    uint8_t *d = call.dev();
+    const hipStream_t s = call.stream();
+    const u32 token = next_done_token();
+    int slot = -1;
+    const int ret = call.roundtrip(out_at, [&] {
+        std::lock_guard<std::mutex> lk(ks->mu);
+        if ((slot = chacha_slot_locked(ks, s)) < 0)
+            return -1;
+        ChaChaArgs a = {};
+        a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
+        a.recs = (const ptls_mi355x_record_t *)d, a.nrecs = 1, a.in = d, a.aad = d, a.out = d, a.ok = d + ok_at;
+        a.claim = nullptr;  // one record, one workgroup: nothing to claim
+        a.done_flag = (u32 *)(d + flag_at), a.done_token = token;
+        chacha_launch_kernel(open, 0, 1, s, a);
+        const hipError_t e = hipGetLastError();
+        (void)hipEventRecord(ks->uses[slot].second, s);
+        return e == hipSuccess ? 0 : fail("chacha single launch: %s", hipGetErrorString(e));
+    }, flag_at, 1, token);
+    if (ret != 0)
+        return -1;
+    if (open) {
+        *verified = h[ok_at] == 1;
+        if (*verified && len != 0)
+            memcpy(output, h + out_at, len);  // a record that failed leaves the caller's output as it was
+    } else {
+        memcpy(output, h + out_at, len + 16);
+    }
+    return 0;
+}
+
+extern "C" {
+
+int ptls_mi355x_chacha_encrypt(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, void *output, const void *input, size_t inlen,
+                               uint64_t seq, const void *aad, size_t aadlen)
+{
+    const ptls_mi355x_iovec_t v = {input, inlen};
+    if (output == NULL || (inlen != 0 && input == NULL))
+        return fail("%s", "chacha encrypt: invalid arguments");
+    return chacha_single(ks, key_idx, false, output, &v, 1, inlen, seq, aad, aadlen, NULL);
+}
+
+int ptls_mi355x_chacha_encrypt_v(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, void *output, const ptls_mi355x_iovec_t *input,
+                                 size_t incnt, uint64_t seq, const void *aad, size_t aadlen)
+{
+    size_t len = 0;
+    if (output == NULL || (incnt != 0 && input == NULL))
+        return fail("%s", "chacha encrypt_v: invalid arguments");
+    for (size_t i = 0; i < incnt; ++i) {
+        if (input[i].len != 0 && input[i].base == NULL)
+            return fail("%s", "chacha encrypt_v: invalid iovec");
+        len += input[i].len;
+    }
+    return chacha_single(ks, key_idx, false, output, input, incnt, len, seq, aad, aadlen, NULL);
+}
+
+size_t ptls_mi355x_chacha_decrypt(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, void *output, const void *input, size_t inlen,
+                                  uint64_t seq, const void *aad, size_t aadlen)
+{
+    if (inlen < 16 || input == NULL)
+        return SIZE_MAX;
+    int verified = 0;
+    const ptls_mi355x_iovec_t v = {input, inlen};
+    if (chacha_single(ks, key_idx, true, output, &v, 1, inlen - 16, seq, aad, aadlen, &verified) != 0)
+        return SIZE_MAX;
+    return verified ? inlen - 16 : SIZE_MAX;
+}
+
+int ptls_mi355x_chacha_hp_mask(ptls_mi355x_chacha_keyset_t *hp_ks, size_t key_idx, void *mask, const void *sample)
+{
+    if (hp_ks == NULL || key_idx >= hp_ks->nkeys || mask == NULL || sample == NULL)
+        return fail("%s", "chacha hp_mask: invalid arguments");
+    DeviceScope scope(hp_ks->device);
+    StageCall call(hp_ks->ds);
+    // staging: [0, 16) sample | [16, 32) entry || [64, 80) mask | [80, 84) done word
+    if (call.acquire(96) != 0)
+        return -1;
+    uint8_t *h = call.host();
+    const ptls_mi355x_hp_t e = {0, (u32)key_idx, 0};
+    memcpy(h, sample, 16);
+    memcpy(h + 16, &e, sizeof(e));
+    memset(h + 80, 0, 4);
+    uint8_t *d = call.dev();
+    const hipStream_t s = call.stream();
+    const u32 token = next_done_token();
+    const int ret = call.roundtrip(64, [&] {
+        std::lock_guard<std::mutex> lk(hp_ks->mu);
+        const int slot = chacha_slot_locked(hp_ks, s);
+        if (slot < 0)
+            return -1;
+        chacha_hp_kernel<<<1, 256, 0, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, (const ptls_mi355x_hp_t *)(d + 16), d, d + 64, 1,
+                                           (u32 *)(d + 80), token);
+        const hipError_t err = hipGetLastError();
+        (void)hipEventRecord(hp_ks->uses[slot].second, s);
+        return err == hipSuccess ? 0 : fail("chacha hp_mask launch: %s", hipGetErrorString(err));
+    }, 80, 1, token);
+    if (ret != 0)
+        return -1;
+    memcpy(mask, h + 64, 16);
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_poly1305(const void *key32, const void *msg, size_t len, void *tag16)
+{
+    if (key32 == NULL || tag16 == NULL || (len != 0 && msg == NULL))
+        return fail("%s", "chacha debug_poly1305: invalid arguments");
+    DeviceState *ds = current_device_state();
+    if (ds == nullptr)
+        return -1;
+    StageCall call(ds);
+    // staging: [0, 32) key | message || tag
+    const size_t tag_at = 32 + ((len + 63) & ~(size_t)63);
+    if (call.acquire(tag_at + 16) != 0)
+        return -1;
+    uint8_t *h = call.host();
+    memcpy(h, key32, 32);
+    if (len != 0)
+        memcpy(h + 32, msg, len);
+    uint8_t *d = call.dev();
+    const hipStream_t s = call.stream();
+    if (call.roundtrip(tag_at, [&] {
+            chacha_poly1305_kernel<<<1, 64, 0, s>>>(d, d + 32, (u64)len, d + tag_at);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }) != 0)
+        return -1;
+    memcpy(tag16, h + tag_at, 16);
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_force(int group_lanes, int max_workgroups)
+{
+    if ((group_lanes != 0 && group_lanes != CHACHA_G_NARROW && group_lanes != CHACHA_G_WIDE) || max_workgroups < 0)
+        return fail("%s", "chacha debug_force: group_lanes is 0, 4 or 16 and max_workgroups is not negative");
+    g_chacha_force_g.store((u32)group_lanes, std::memory_order_relaxed);
+    g_chacha_force_wgs.store((u32)max_workgroups, std::memory_order_relaxed);
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_counters(uint64_t *out, int reset)
+{
+    if (out == NULL)
+        return fail("%s", "chacha debug_counters: invalid arguments");
+    HIP_TRY(hipDeviceSynchronize());  // (test-only) every launch made so far has counted itself
+    unsigned long long n[2] = {0, 0};
+    HIP_TRY(hipMemcpyFromSymbol(n, HIP_SYMBOL(g_chacha_launches), sizeof(n)));
+    out[0] = n[0], out[1] = n[1];
+    if (reset) {
+        n[0] = n[1] = 0;
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_chacha_launches), n, sizeof(n)));
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+#endif  // PTLS_MI355X_CHACHA_HOST_H

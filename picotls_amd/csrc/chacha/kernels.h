@@ -1,0 +1,354 @@
+// picotls_amd/csrc/chacha/kernels.h -- ChaCha20-Poly1305 (RFC 8439 §2.8) seal / open of a batch of records, the QUIC
+// header-protection masks of that suite and the Poly1305 test hook.
+// Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip (included after chacha20.h and poly1305.h).
+//
+// Shape. One persistent launch per batch; a workgroup claims runs of records from an atomic counter, its
+// waves take 64 / G records of the run at a time and a group of G lanes owns one record. Lane j of the group runs the
+// ChaCha20 blocks with counter j, j + G, ...: counter 0 (lane 0's first block) is the one-time Poly1305 key, counter
+// v >= 1 the keystream of the 64 text bytes from 64 (v - 1), so in each step the group touches G x 64 contiguous bytes.
+// No tables: the cipher is add, xor and rotate on registers, nothing is addressed by secret data, and the LDS holds
+// only the workgroup's current claim and the four partial sums of its width sample.
+//
+// Poly1305 across the group. The tag is sum m_i r^(N - i) + s over the 16-byte blocks of pad16(AAD) || pad16(text) ||
+// LE64(aadlen) || LE64(textlen). A lane folds the four Poly1305 blocks of each of its 64-byte blocks into its own
+// accumulator: (h + m) r three times, then (h + m) r^(4G - 3), which carries it over the other lanes' blocks to its next
+// one. The lane that owns text block 0 (lane 1) starts its chain with the AAD blocks. After its last block a lane
+// multiplies by r^E, E = the number of text blocks from that block to the end (1 .. 4G - 3), which aligns every lane's
+// partial with the position of the length block; the partials are added across the group, the length block is added
+// and one multiplication by r, one reduction mod 2^130 - 5 and the addition of s finish the tag. r^(4G - 3) and r^E come
+// from log2(4G) - 1 squarings of r per record.
+#ifndef PTLS_MI355X_CHACHA_KERNELS_H
+#define PTLS_MI355X_CHACHA_KERNELS_H
+
+#define CHACHA_WG 256            // threads per workgroup
+#define CHACHA_G_NARROW 4        // lanes per record: QUIC-sized records (19 blocks at 1200 B: 20 with the key block, 5 a lane)
+#define CHACHA_G_WIDE 16         // ... and long ones (16 KiB: 257 blocks, 16 or 17 a lane)
+#define CHACHA_WIDE_MIN 4096u    // a workgroup takes the wide groups when its sample of the batch averages this length
+#define CHACHA_TLS_MAX_PLAIN 16384u
+
+struct ChaChaArgs {
+    const ChaChaKey *keys;
+    u32 nkeys;
+    u32 force_g;  // 0: each workgroup chooses from a sample of the descriptors
+    const ptls_mi355x_record_t *recs;
+    u64 nrecs;
+    const uint8_t *in, *aad;
+    uint8_t *out, *ok;
+    // [0] the next unclaimed record, [1] workgroups that have finished; both zero between launches (the last workgroup
+    // to finish clears them). Null: rounds of records are dealt to the workgroups by index instead.
+    unsigned long long *claim;
+    u32 *done_flag;  // per-record path: one completion word per workgroup (publish_done)
+    u32 done_token;
+};
+
+// launches per group width (ptls_mi355x_chacha_debug_counters): [0] narrow, [1] wide, counted by workgroup 0
+__device__ unsigned long long g_chacha_launches[2];
+
+__device__ __forceinline__ u32 sub_clamp16(u32 n, u32 off) { return n > off ? min(n - off, 16u) : 0u; }
+
+template <int G, bool OPEN, int FRAME>
+__device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 j)
+{
+    static_assert(G >= 2 && G <= 64 && (G & (G - 1)) == 0, "group width");
+    constexpr u32 STRIDE_E = 4 * G - 3;          // exponent that carries a lane from its block's end to its next block
+    constexpr int NBITS = __builtin_ctz(4 * G);  // bits of the exponents 1 .. 4G - 3
+    const bool valid = idx < a.nrecs;
+    ptls_mi355x_record_t r = {};
+    if (valid)
+        r = a.recs[idx];
+    const u32 A = FRAME ? (u32)TLS_HEADER_SIZE : PTLS_MI355X_RECORD_AAD_LEN(&r);
+    const u32 T = r.len + (FRAME && !OPEN ? 1u : 0u);  // text bytes (TLS seal: the payload and the inner content type)
+    // a descriptor beyond the limits is rejected: nothing is written for it and open reports ok = 0
+    const bool good = valid && r.len <= PTLS_MI355X_MAX_RECORD_LEN && A <= PTLS_MI355X_MAX_AAD_LEN && r.key_idx < a.nkeys &&
+                      (FRAME == 0 || OPEN || r.len <= CHACHA_TLS_MAX_PLAIN) && (FRAME != 0 || A == 0 || a.aad != nullptr);
+    const ChaChaKey *ke = a.keys + (good ? r.key_idx : 0);
+    u32 key[8];
+    {
+        const u32x4 k0 = *(const u32x4 *)&ke->key[0], k1 = *(const u32x4 *)&ke->key[4];
+        key[0] = k0.x, key[1] = k0.y, key[2] = k0.z, key[3] = k0.w;
+        key[4] = k1.x, key[5] = k1.y, key[6] = k1.z, key[7] = k1.w;
+    }
+    // nonce = static IV ^ (0^32 || BE64(seq))
+    const u32 n0 = ke->iv[0], n1 = ke->iv[1] ^ bswap32((u32)(r.seq >> 32)), n2 = ke->iv[2] ^ bswap32((u32)r.seq);
+    const uint8_t *src = a.in + r.in_off + (FRAME && OPEN ? TLS_HEADER_SIZE : 0);
+    uint8_t *dst = a.out + r.out_off + (FRAME && !OPEN ? TLS_HEADER_SIZE : 0);
+    const u32 Cb = (T + 63) >> 6, C = (T + 15) >> 4;  // 64-byte blocks, 16-byte blocks of the text
+
+    // the lane's first block: counter j (lane 0: the Poly1305 key block, whose r and s go to the whole group)
+    u32 x[16];
+    chacha20_block(key, j, n0, n1, n2, x);
+    u32 otk[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        otk[i] = (u32)__shfl((int)x[i], 0, G);
+    const Fe r1 = fe_clamped_r(otk[0], otk[1], otk[2], otk[3]);
+
+    // the lane's last text block and the exponent E that aligns its partial
+    const u32 b0 = j == 0 ? (u32)G - 1 : j - 1;
+    u32 E = 0;
+    if (b0 < Cb) {
+        const u32 blast = b0 + ((Cb - 1 - b0) & ~((u32)G - 1));
+        const u32 nblast = (min(64u, T - 64 * blast) + 15) >> 4;
+        E = C - (4 * blast + nblast - 1);
+    }
+    Fe rE = fe_select((E & 1) != 0, r1, fe_one()), rS = r1, sq = r1;
+#pragma unroll
+    for (int bit = 1; bit < NBITS; ++bit) {
+        sq = fe_mul(sq, sq);
+        rE = fe_select(((E >> bit) & 1) != 0, fe_mul(rE, sq), rE);
+        if ((STRIDE_E >> bit) & 1)
+            rS = fe_mul(rS, sq);
+    }
+
+    Fe h = fe_zero();
+    // one 64-byte block b of the text, keystream in x: crypt it, then fold its 16-byte blocks into h
+    auto text_block = [&](u32 b) {
+        const u32 o = 64 * b, nT = min(64u, T - o);
+        const u32 nS = FRAME && !OPEN ? (r.len > o ? min(64u, r.len - o) : 0u) : nT;  // bytes the input holds
+        u32x4 c[4];
+        if (nT == 64 && nS == 64) {  // a whole block: four 16-byte accesses, nothing to clamp or mask
+#pragma unroll
+            for (u32 w = 0; w < 4; ++w) {
+                const u32x4 p = *(const u32x4_u *)(src + o + 16 * w);
+                const u32x4 ks = {x[4 * w], x[4 * w + 1], x[4 * w + 2], x[4 * w + 3]};
+                const u32x4 q = p ^ ks;
+                *(u32x4_u *)(dst + o + 16 * w) = q;
+                c[w] = OPEN ? p : q;
+            }
+        } else
+#pragma unroll
+        for (u32 w = 0; w < 4; ++w) {
+            const u32 ns = sub_clamp16(nS, 16 * w), nt = sub_clamp16(nT, 16 * w);
+            u32x4 p = load_upto16(src + o + 16 * w, ns);
+            if (FRAME && !OPEN && r.len - o - 16 * w < 16) {  // the inner content type follows the payload
+                const u32 at = r.len - o - 16 * w, t = (u32)(r.flags & 0xff) << (8 * (at & 3));
+#pragma unroll
+                for (u32 k = 0; k < 4; ++k)
+                    p[k] |= (at >> 2) == k ? t : 0u;
+            }
+            const u32x4 ks = {x[4 * w], x[4 * w + 1], x[4 * w + 2], x[4 * w + 3]};
+            const u32x4 q = p ^ ks;
+            store_upto16(dst + o + 16 * w, q, nt);
+            c[w] = OPEN ? p : keep_bytes(q, nt);  // the ciphertext, zero from its end
+        }
+        const u32 nb = (nT + 15) >> 4;
+        if (nb == 4 && b + G < Cb) {
+            fe_add_block(h, c[0].x, c[0].y, c[0].z, c[0].w, 1), h = fe_mul(h, r1);
+            fe_add_block(h, c[1].x, c[1].y, c[1].z, c[1].w, 1), h = fe_mul(h, r1);
+            fe_add_block(h, c[2].x, c[2].y, c[2].z, c[2].w, 1), h = fe_mul(h, r1);
+            fe_add_block(h, c[3].x, c[3].y, c[3].z, c[3].w, 1), h = fe_mul(h, rS);
+        } else {  // the lane's last block (the only one that may be short)
+#pragma unroll
+            for (u32 t = 0; t < 4; ++t) {
+                if (t < nb) {
+                    fe_add_block(h, c[t].x, c[t].y, c[t].z, c[t].w, 1);
+                    h = fe_mul(h, fe_select(t + 1 < nb, r1, rE));
+                }
+            }
+        }
+    };
+
+    if (good) {
+        if (j == 1) {  // the owner of text block 0 starts with the AAD
+            if (FRAME) {
+                u32 w0, w1;
+                if (OPEN) {  // the header as received
+                    const uint8_t *hp = a.in + r.in_off;
+                    w0 = (u32)hp[0] | (u32)hp[1] << 8 | (u32)hp[2] << 16 | (u32)hp[3] << 24, w1 = hp[4];
+                } else {  // {23, 3, 3, BE16(len + 17)}
+                    const u32 wire = r.len + 17;
+                    uint8_t *hp = a.out + r.out_off;
+                    w0 = 23u | 3u << 8 | 3u << 16 | (wire >> 8) << 24, w1 = wire & 0xff;
+                    hp[0] = 23, hp[1] = 3, hp[2] = 3, hp[3] = (uint8_t)(wire >> 8), hp[4] = (uint8_t)wire;
+                }
+                fe_add_block(h, w0, w1, 0, 0, 1), h = fe_mul(h, r1);
+            } else {
+                const uint8_t *ap = a.aad + r.aad_off;
+                for (u32 off = 0; off < A; off += 16) {
+                    const u32x4 w = load_upto16(ap + off, min(16u, A - off));
+                    fe_add_block(h, w.x, w.y, w.z, w.w, 1), h = fe_mul(h, r1);
+                }
+            }
+        }
+        if (j >= 1 && j - 1 < Cb)
+            text_block(j - 1);
+        for (u32 v = j + G; v <= Cb; v += G) {
+            chacha20_block(key, v, n0, n1, n2, x);
+            text_block(v - 1);
+        }
+    }
+
+    // every lane of the wave is here: the partials of the group, summed into all its lanes
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+#pragma unroll
+        for (int m = 1; m < G; m <<= 1)
+            h.v[i] += (u32)__shfl_xor((int)h.v[i], m, G);
+    }
+    if (good && j == 0) {
+        fe_add_block(h, A, 0, T, 0, 1);  // LE64(aadlen) || LE64(textlen)
+        h = fe_mul(h, r1);
+        u32 tag[4];
+        fe_tag(h, &otk[4], tag);
+        if (OPEN) {
+            // all 16 bytes compared, no early exit
+            const u32x4 got = *(const u32x4_u *)(src + T);
+            const u32 diff = (got.x ^ tag[0]) | (got.y ^ tag[1]) | (got.z ^ tag[2]) | (got.w ^ tag[3]);
+            a.ok[idx] = diff == 0;
+        } else {
+            const u32x4 t = {tag[0], tag[1], tag[2], tag[3]};
+            *(u32x4_u *)(dst + T) = t;
+        }
+    } else if (OPEN && valid && j == 0) {
+        a.ok[idx] = 0;
+    }
+}
+
+// The workgroup's share of the batch. One claim is a run of consecutive records, CHACHA_CLAIMS_PER_WG claims a workgroup
+// on average: a claim is one atomic on one address for the whole device, which the memory side serves at some 28 ns
+// each (a wave claiming its own 64 / G records made 65,536 claims a launch of 2^20 QUIC packets and spent most of the
+// launch queueing for them), so a workgroup claims for its four waves at once and in runs of several rounds. The waves
+// of a workgroup take the records of a claim round by round, 64 / G each.
+#define CHACHA_CLAIMS_PER_WG 8
+template <int G, bool OPEN, int FRAME>
+__device__ __forceinline__ void chacha_records(const ChaChaArgs &a, unsigned long long *s_base)
+{
+    constexpr u32 PER_WAVE = 64 / G, PER_ROUND = CHACHA_WG / G;
+    const u32 lane = threadIdx.x & 63, j = lane % G, grp = lane / G, wave = threadIdx.x / 64;
+    const u64 rounds = a.nrecs / ((u64)gridDim.x * CHACHA_CLAIMS_PER_WG * PER_ROUND);
+    const u64 run = a.claim != nullptr ? max(rounds, (u64)1) * PER_ROUND : PER_ROUND;
+    // one round of the workgroup per iteration; a new run is claimed when the current one is used up
+    u64 cur = (u64)blockIdx.x * PER_ROUND, end = a.claim != nullptr ? 0 : cur + PER_ROUND;
+    if (a.claim != nullptr)
+        cur = 0;
+    for (;;) {
+        if (cur >= end) {
+            if (a.claim != nullptr) {
+                __syncthreads();  // every wave has read the last claim
+                if (threadIdx.x == 0)
+                    *s_base = atomicAdd(a.claim, (unsigned long long)run);
+                __syncthreads();
+                const unsigned long long b = *s_base;  // (the same in every lane: kept in scalar registers)
+                cur = (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)b) |
+                      (u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(b >> 32)) << 32;
+            } else {  // no counter (the per-record path): rounds dealt by workgroup index
+                cur += (u64)(gridDim.x - 1) * PER_ROUND;
+            }
+            end = cur + run;
+        }
+        if (cur >= a.nrecs)
+            break;
+        chacha_record<G, OPEN, FRAME>(a, cur + wave * PER_WAVE + grp, j);
+        cur += PER_ROUND;
+    }
+}
+
+template <bool OPEN, int FRAME>
+__global__ __launch_bounds__(CHACHA_WG) void chacha_batch_kernel(ChaChaArgs a)
+{
+    __shared__ u32 s_len[CHACHA_WG / 64];
+    __shared__ unsigned long long s_base;
+    unsigned long long *const kclock = ENGINE_HOOKS && blockIdx.x == 0 ? g_kclock_buf : nullptr;
+    const u64 kc_t0 = kclock != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
+    const u64 kc_r0 = kclock != nullptr ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    u32 g = a.force_g;
+    if (g == 0) {
+        // the width from the mean length of CHACHA_WG descriptors spread over the batch (every workgroup reads the
+        // same ones; nothing depends on the workgroups agreeing, a claim is a run of records whatever G takes it)
+        u32 len = min(a.recs[(u64)threadIdx.x * a.nrecs / CHACHA_WG].len, PTLS_MI355X_MAX_RECORD_LEN >> 8);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1)
+            len += (u32)__shfl_xor((int)len, m);
+        if ((threadIdx.x & 63) == 0)
+            s_len[threadIdx.x / 64] = len;
+        __syncthreads();
+        u32 sum = 0;
+#pragma unroll
+        for (int w = 0; w < CHACHA_WG / 64; ++w)
+            sum += s_len[w];
+        g = sum / CHACHA_WG >= CHACHA_WIDE_MIN ? CHACHA_G_WIDE : CHACHA_G_NARROW;
+    }
+    if (g == CHACHA_G_WIDE)
+        chacha_records<CHACHA_G_WIDE, OPEN, FRAME>(a, &s_base);
+    else
+        chacha_records<CHACHA_G_NARROW, OPEN, FRAME>(a, &s_base);
+    if (ENGINE_HOOKS && blockIdx.x == 0 && threadIdx.x == 0)
+        atomicAdd(&g_chacha_launches[g == CHACHA_G_WIDE ? 1 : 0], 1ull);
+    if (a.claim != nullptr) {
+        __syncthreads();  // this workgroup has made its last claim
+        if (threadIdx.x == 0 && atomicAdd(a.claim + 1, 1ull) == gridDim.x - 1) {
+            atomicExch(a.claim, 0ull);
+            atomicExch(a.claim + 1, 0ull);
+        }
+    }
+    if (kclock != nullptr && threadIdx.x == 0) {
+        const u64 t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+        const u32 i = atomicAdd(&g_kclock_n, 1u);
+        if (i < g_kclock_cap) {
+            kclock[4 * i + 0] = kc_t0, kclock[4 * i + 1] = t1;
+            kclock[4 * i + 2] = kc_r0, kclock[4 * i + 3] = r1;
+        }
+    }
+    publish_done(a.done_flag, a.done_token);
+}
+
+// QUIC header protection for the ChaCha20 suites: one lane per sample, one block. The sample's first 4 bytes are the
+// block counter (little endian) and the next 12 the nonce (picotls' 16-byte ChaCha20 IV, include/picotls.h:95); the mask
+// is the first 16 keystream bytes. An entry whose key_idx is out of range gets a zero mask.
+__global__ __launch_bounds__(256) void chacha_hp_kernel(const ChaChaKey *keys, u32 nkeys, const ptls_mi355x_hp_t *hp,
+                                                        const uint8_t *base, uint8_t *masks, u64 n, u32 *done_flag, u32 done_token)
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const ptls_mi355x_hp_t e = hp[i];
+        u32x4 m = {0, 0, 0, 0};
+        if (e.key_idx < nkeys) {
+            const u32x4 s = *(const u32x4_u *)(base + e.sample_off);
+            const ChaChaKey *ke = keys + e.key_idx;
+            u32 key[8], x[16];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                key[k] = ke->key[k];
+            chacha20_block(key, s.x, s.y, s.z, s.w, x);
+            m.x = x[0], m.y = x[1], m.z = x[2], m.w = x[3];
+        }
+        *(u32x4_u *)(masks + 16 * i) = m;
+    }
+    publish_done(done_flag, done_token);
+}
+
+// rekey (ptls_mi355x_chacha_keyset_update): entry idx[i] = src[i]
+__global__ __launch_bounds__(256) void chacha_keys_scatter_kernel(const ChaChaKey *src, const u32 *idx, ChaChaKey *dst, u32 n)
+{
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n)
+        dst[idx[i]] = src[i];
+}
+
+// Test hook (ptls_mi355x_chacha_debug_poly1305): plain Poly1305 (RFC 8439 §2.5) of msg under a given one-time key, one
+// lane, with the routines the record kernels use. A short last block takes the byte 1 after its end and no 2^128 bit.
+__global__ __launch_bounds__(64) void chacha_poly1305_kernel(const uint8_t *key, const uint8_t *msg, u64 len, uint8_t *tag)
+{
+    if (threadIdx.x != 0)
+        return;
+    const u32x4 k0 = *(const u32x4_u *)key, k1 = *(const u32x4_u *)(key + 16);
+    const Fe r = fe_clamped_r(k0.x, k0.y, k0.z, k0.w);
+    const u32 s[4] = {k1.x, k1.y, k1.z, k1.w};
+    Fe h = fe_zero();
+    for (u64 off = 0; off < len; off += 16) {
+        const u32 n = (u32)min((u64)16, len - off);
+        u32x4 w = load_upto16(msg + off, n);
+        if (n < 16) {
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k)
+                w[k] |= (n >> 2) == k ? 1u << (8 * (n & 3)) : 0u;
+        }
+        fe_add_block(h, w.x, w.y, w.z, w.w, n == 16);
+        h = fe_mul(h, r);
+    }
+    u32 t[4];
+    fe_tag(h, s, t);
+    const u32x4 o = {t[0], t[1], t[2], t[3]};
+    *(u32x4_u *)tag = o;
+}
+
+#endif  // PTLS_MI355X_CHACHA_KERNELS_H
