@@ -1,6 +1,6 @@
 // picotls_amd/csrc/chacha/host.h -- host side of the ChaCha20-Poly1305 engine: the C ABI of
 // include/picotls/mi355x_chacha20.h. Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip, included
-// last: it uses that file's per-device state, streams, event pool, staging pool (StageCall) and error reporting.
+// last: built on host/runtime.h (per-device state, streams, event pool, StreamUses, StreamSlots, StageCall, error reporting).
 #ifndef PTLS_MI355X_CHACHA_HOST_H
 #define PTLS_MI355X_CHACHA_HOST_H
 
@@ -8,8 +8,8 @@
 #define CHACHA_CLAIM_SLOTS 8  // claim counters per keyset: one per stream in use, shared in stream order beyond that
 
 // A keyset is the entry array and, behind it, its claim counters (a pair of u64 per slot, zero between launches).
-// Launches on one stream run in order and share a slot; a stream without one takes a free slot, or takes a slot over
-// after waiting for its last launch.
+// Launches on one stream run in order and share a slot; a stream without one takes a free slot, or takes the least
+// recently used one over after waiting for the last launch of the stream that held it (StreamSlots).
 struct st_ptls_mi355x_chacha_keyset_t {
     DeviceState *ds = nullptr;
     int device = 0;
@@ -17,39 +17,35 @@ struct st_ptls_mi355x_chacha_keyset_t {
     ChaChaKey *d_keys = nullptr;
     unsigned long long *d_claim = nullptr;
     std::vector<uint8_t> ivs;  // the static IVs (get_iv reads these; the device copy is what seals use)
-    std::mutex mu;             // launches from several threads: the slots below
-    std::vector<std::pair<hipStream_t, hipEvent_t>> uses;  // slot i: its stream, and the event after its last launch
-    unsigned takeover = 0;
+    std::mutex mu;             // launches from several threads: the two below, held from taking a slot through the
+                               // launch and the use event after it
+    StreamUses uses;           // per stream: after this keyset's last launch on it (teardown and rekey wait for these)
+    StreamSlots<unsigned, CHACHA_CLAIM_SLOTS> slots;  // per stream: the index of its claim slot
 };
 
 static std::atomic<u32> g_chacha_force_g{0}, g_chacha_force_wgs{0};
 
-// the claim slot of `s` (ks->mu held); a slot taken over from another stream is first waited for
-static int chacha_slot_locked(ptls_mi355x_chacha_keyset_t *ks, hipStream_t s)
+// `launch()` on `s` and the keyset's use after it (ks->mu held); a launch error is reported through `fmt`
+template <typename Launch>
+static int chacha_launch_noted(ptls_mi355x_chacha_keyset_t *ks, hipStream_t s, const char *fmt, Launch launch)
 {
-    for (size_t i = 0; i < ks->uses.size(); ++i)
-        if (ks->uses[i].first == s)
-            return (int)i;
-    if (ks->uses.size() < CHACHA_CLAIM_SLOTS) {
-        hipEvent_t e = event_get(ks->ds);
-        if (e == nullptr)
-            return fail("%s", "event creation failed");
-        ks->uses.emplace_back(s, e);
-        return (int)ks->uses.size() - 1;
-    }
-    const int i = (int)(ks->takeover++ % CHACHA_CLAIM_SLOTS);
-    HIP_TRY(hipStreamWaitEvent(s, ks->uses[i].second, 0));
-    ks->uses[i].first = s;
-    return i;
+    return launch_and_note(ks->uses, ks->ds, s, [&] {
+        LAUNCH_CLEAR();
+        launch();
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? 0 : fail(fmt, hipGetErrorString(e));
+    });
 }
 
-// orders the maintenance stream after every launch that used the keyset
-static int chacha_maint_after_uses(ptls_mi355x_chacha_keyset_t *ks)
+static std::vector<ChaChaKey> chacha_entries(const void *keys, const void *ivs, size_t n)  // (the caller clears them)
 {
-    std::lock_guard<std::mutex> lk(ks->mu);
-    for (auto &u : ks->uses)
-        HIP_TRY(hipStreamWaitEvent(ks->ds->maint, u.second, 0));
-    return 0;
+    std::vector<ChaChaKey> host(n);
+    for (size_t i = 0; i < n; ++i) {
+        memset(&host[i], 0, sizeof(ChaChaKey));
+        memcpy(host[i].key, (const uint8_t *)keys + i * 32, 32);
+        memcpy(host[i].iv, (const uint8_t *)ivs + i * 12, 12);
+    }
+    return host;
 }
 
 static unsigned chacha_grid(const DeviceState *ds, size_t nrecs)
@@ -64,17 +60,9 @@ static unsigned chacha_grid(const DeviceState *ds, size_t nrecs)
 
 static void chacha_launch_kernel(bool open, int frame, unsigned grid, hipStream_t s, const ChaChaArgs &a)
 {
-    if (frame == 0) {
-        if (open)
-            chacha_batch_kernel<true, 0><<<grid, CHACHA_WG, 0, s>>>(a);
-        else
-            chacha_batch_kernel<false, 0><<<grid, CHACHA_WG, 0, s>>>(a);
-    } else {
-        if (open)
-            chacha_batch_kernel<true, 1><<<grid, CHACHA_WG, 0, s>>>(a);
-        else
-            chacha_batch_kernel<false, 1><<<grid, CHACHA_WG, 0, s>>>(a);
-    }
+    with_either<0, 1>(frame, [&](auto FRAME) {
+        with_bool(open, [&](auto OPEN) { chacha_batch_kernel<OPEN, FRAME><<<grid, CHACHA_WG, 0, s>>>(a); });
+    });
 }
 
 static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int frame, const ptls_mi355x_record_t *recs, size_t nrecs,
@@ -87,21 +75,15 @@ static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int f
     DeviceScope scope(ks->device);
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(ks->mu);
-    const int slot = chacha_slot_locked(ks, s);
-    if (slot < 0)
+    const unsigned *slot = ks->slots.get(s, ks->uses, [&](unsigned &i) { return i = (unsigned)ks->slots.v.size(), true; });
+    if (slot == nullptr)
         return -1;
     ChaChaArgs a = {};
     a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
     a.recs = recs, a.nrecs = nrecs, a.in = (const uint8_t *)in, a.aad = (const uint8_t *)aad, a.out = (uint8_t *)out, a.ok = ok;
-    a.claim = ks->d_claim + 2 * slot;
-    LAUNCH_CLEAR();
-    chacha_launch_kernel(open, frame, chacha_grid(ks->ds, nrecs), s, a);
-    const hipError_t e = hipGetLastError();
-    // (the use is recorded either way: teardown and a takeover of the slot wait for whatever was queued)
-    const hipError_t rec = hipEventRecord(ks->uses[slot].second, s);
-    if (e != hipSuccess)
-        return fail("chacha batch launch: %s", hipGetErrorString(e));
-    return rec == hipSuccess ? 0 : fail("%s", "hipEventRecord failed");
+    a.claim = ks->d_claim + 2 * *slot;
+    const unsigned grid = chacha_grid(ks->ds, nrecs);
+    return chacha_launch_noted(ks, s, "chacha batch launch: %s", [&] { chacha_launch_kernel(open, frame, grid, s, a); });
 }
 
 extern "C" {
@@ -122,12 +104,8 @@ ptls_mi355x_chacha_keyset_t *ptls_mi355x_chacha_keyset_new(const void *keys, con
     }
     ks->ds = ds, ks->device = ds->device, ks->nkeys = nkeys;
     ks->ivs.assign((const uint8_t *)ivs, (const uint8_t *)ivs + nkeys * 12);
-    std::vector<ChaChaKey> host(nkeys);
-    for (size_t i = 0; i < nkeys; ++i) {
-        memset(&host[i], 0, sizeof(ChaChaKey));
-        memcpy(host[i].key, (const uint8_t *)keys + i * 32, 32);
-        memcpy(host[i].iv, (const uint8_t *)ivs + i * 12, 12);
-    }
+    std::vector<ChaChaKey> host = chacha_entries(keys, ivs, nkeys);
+    free_after_maint(ds, nullptr);  // (entries of freed keysets whose clearing has run go back to the pool)
     // entries and counters in stream-ordered memory on the setup stream; the call waits for that stream only
     const size_t kbytes = nkeys * sizeof(ChaChaKey), cbytes = CHACHA_CLAIM_SLOTS * 2 * sizeof(unsigned long long);
     const bool ok = hipMallocAsync((void **)&ks->d_keys, kbytes + cbytes, ds->setup) == hipSuccess &&
@@ -156,18 +134,11 @@ void ptls_mi355x_chacha_keyset_free(ptls_mi355x_chacha_keyset_t *ks)
     DeviceState *ds = ks->ds;
     // the key material is cleared after the keyset's last launch, on the maintenance stream; where that order cannot be
     // set up on the device the host waits for the launches instead, and failing that too the entries are left as they are
-    bool ordered = chacha_maint_after_uses(ks) == 0;
-    if (!ordered) {
-        ordered = true;
-        for (auto &u : ks->uses)
-            ordered = hipEventSynchronize(u.second) == hipSuccess && ordered;
-    }
-    if (ordered) {
+    if (std::lock_guard<std::mutex> lk(ks->mu); ks->uses.order_after_all(ds->maint) == 0 || ks->uses.drain()) {
         (void)hipMemsetAsync(ks->d_keys, 0, ks->nkeys * sizeof(ChaChaKey), ds->maint);
-        (void)hipFreeAsync(ks->d_keys, ds->maint);
+        free_after_maint(ds, ks->d_keys);
     }
-    for (auto &u : ks->uses)
-        event_put(ds, u.second);
+    ks->uses.release(ds);
     clear_memory(ks->ivs.data(), ks->ivs.size());
     delete ks;
 }
@@ -180,27 +151,16 @@ int ptls_mi355x_chacha_keyset_update(ptls_mi355x_chacha_keyset_t *ks, const uint
 {
     if (ks == NULL || (n != 0 && (key_idx == NULL || keys == NULL || ivs == NULL)))
         return fail("%s", "chacha keyset_update: invalid arguments");
-    std::vector<bool> seen(n != 0 ? ks->nkeys : 0);
-    for (size_t i = 0; i < n; ++i) {
-        if (key_idx[i] >= ks->nkeys)
-            return fail("%s", "chacha keyset_update: key index out of range");
-        if (seen[key_idx[i]])
-            return fail("%s", "chacha keyset_update: key index listed twice");
-        seen[key_idx[i]] = true;
-    }
+    if (check_update_indices("chacha keyset_update", key_idx, n, ks->nkeys) != 0)
+        return -1;
     if (n == 0)
         return 0;
     DeviceScope scope(ks->device);
     DeviceState *ds = ks->ds;
-    std::vector<ChaChaKey> host(n);
-    for (size_t i = 0; i < n; ++i) {
-        memset(&host[i], 0, sizeof(ChaChaKey));
-        memcpy(host[i].key, (const uint8_t *)keys + i * 32, 32);
-        memcpy(host[i].iv, (const uint8_t *)ivs + i * 12, 12);
-    }
+    std::vector<ChaChaKey> host = chacha_entries(keys, ivs, n);
     // on the maintenance stream, after every launch already made with the old entries; the call returns once the
     // scatter has run, so launches made after it see the new ones
-    if (chacha_maint_after_uses(ks) != 0)
+    if (std::lock_guard<std::mutex> lk(ks->mu); ks->uses.order_after_all(ds->maint) != 0)
         return -1;
     uint8_t *d = NULL;
     const size_t kb = n * sizeof(ChaChaKey), sb = n * 4;
@@ -239,7 +199,7 @@ int ptls_mi355x_chacha_keyset_set_iv(ptls_mi355x_chacha_keyset_t *ks, size_t key
     if (ks == NULL || key_idx >= ks->nkeys || iv == NULL)
         return fail("%s", "chacha set_iv: bad key index");
     DeviceScope scope(ks->device);
-    if (chacha_maint_after_uses(ks) != 0)
+    if (std::lock_guard<std::mutex> lk(ks->mu); ks->uses.order_after_all(ks->ds->maint) != 0)
         return -1;
     HIP_TRY(hipMemcpyAsync(ks->d_keys[key_idx].iv, iv, 12, hipMemcpyHostToDevice, ks->ds->maint));
     HIP_TRY(hipStreamSynchronize(ks->ds->maint));
@@ -291,17 +251,10 @@ int ptls_mi355x_chacha_hp_mask_batch(ptls_mi355x_chacha_keyset_t *hp_ks, const p
     DeviceScope scope(hp_ks->device);
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(hp_ks->mu);
-    const int slot = chacha_slot_locked(hp_ks, s);  // (for its use event: teardown and rekey wait for this launch)
-    if (slot < 0)
-        return -1;
-    LAUNCH_CLEAR();
-    chacha_hp_kernel<<<aux_grid(n, hp_ks->ds->ncu), 256, 0, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, hp, (const uint8_t *)base,
-                                                                 (uint8_t *)masks, n, nullptr, 0);
-    const hipError_t e = hipGetLastError();
-    const hipError_t rec = hipEventRecord(hp_ks->uses[slot].second, s);
-    if (e != hipSuccess)
-        return fail("chacha hp_mask launch: %s", hipGetErrorString(e));
-    return rec == hipSuccess ? 0 : fail("%s", "hipEventRecord failed");
+    return chacha_launch_noted(hp_ks, s, "chacha hp_mask launch: %s", [&] {
+        chacha_hp_kernel<<<aux_grid(n, hp_ks->ds->ncu), 256, 0, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, hp, (const uint8_t *)base,
+                                                                     (uint8_t *)masks, n, nullptr, 0);
+    });
 }
 
 }  // extern "C"
@@ -310,10 +263,8 @@ int ptls_mi355x_chacha_hp_mask_batch(ptls_mi355x_chacha_keyset_t *hp_ks, const p
 static int chacha_single(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, bool open, void *output, const ptls_mi355x_iovec_t *vec,
                          size_t incnt, size_t len, uint64_t seq, const void *aad, size_t aadlen, int *verified)
 {
-    if (ks == NULL || key_idx >= ks->nkeys || (aadlen != 0 && aad == NULL) || (len != 0 && output == NULL))
-        return fail("%s", "chacha single: invalid arguments");
-    if (len > PTLS_MI355X_MAX_RECORD_LEN || aadlen > PTLS_MI355X_MAX_AAD_LEN)
-        return fail("%s", "chacha single: record or AAD longer than PTLS_MI355X_MAX_RECORD_LEN / PTLS_MI355X_MAX_AAD_LEN");
+    if (check_single_args("chacha single", ks != NULL && key_idx < ks->nkeys, aad, aadlen, output, len) != 0)
+        return -1;
     DeviceScope scope(ks->device);
     StageCall call(ks->ds);
     // staging: [0, 40) descriptor | AAD | input (open: with the tag) || output (seal: with the tag) | ok byte | done word
@@ -329,32 +280,21 @@ static int chacha_single(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, bool o
     memcpy(h, &rec, sizeof(rec));
     if (aadlen != 0)
         memcpy(h + aad_at, aad, aadlen);
-    size_t at = in_at;
-    for (size_t i = 0; i < incnt; ++i) {
-        if (vec[i].len != 0)
-            memcpy(h + at, vec[i].base, vec[i].len);
-        at += vec[i].len;
-    }
+    gather_iovec(h + in_at, vec, incnt);
     h[ok_at] = 0;
     memset(h + flag_at, 0, 4);
     call.clear_lo = in_at, call.clear_hi = ok_at;
     uint8_t *d = call.dev();
     const hipStream_t s = call.stream();
     const u32 token = next_done_token();
-    int slot = -1;
     const int ret = call.roundtrip(out_at, [&] {
-        std::lock_guard<std::mutex> lk(ks->mu);
-        if ((slot = chacha_slot_locked(ks, s)) < 0)
-            return -1;
         ChaChaArgs a = {};
         a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
         a.recs = (const ptls_mi355x_record_t *)d, a.nrecs = 1, a.in = d, a.aad = d, a.out = d, a.ok = d + ok_at;
-        a.claim = nullptr;  // one record, one workgroup: nothing to claim
+        a.claim = nullptr;  // one record, one workgroup: nothing to claim, so no claim slot either
         a.done_flag = (u32 *)(d + flag_at), a.done_token = token;
-        chacha_launch_kernel(open, 0, 1, s, a);
-        const hipError_t e = hipGetLastError();
-        (void)hipEventRecord(ks->uses[slot].second, s);
-        return e == hipSuccess ? 0 : fail("chacha single launch: %s", hipGetErrorString(e));
+        std::lock_guard<std::mutex> lk(ks->mu);
+        return chacha_launch_noted(ks, s, "chacha single launch: %s", [&] { chacha_launch_kernel(open, 0, 1, s, a); });
     }, flag_at, 1, token);
     if (ret != 0)
         return -1;
@@ -424,14 +364,10 @@ int ptls_mi355x_chacha_hp_mask(ptls_mi355x_chacha_keyset_t *hp_ks, size_t key_id
     const u32 token = next_done_token();
     const int ret = call.roundtrip(64, [&] {
         std::lock_guard<std::mutex> lk(hp_ks->mu);
-        const int slot = chacha_slot_locked(hp_ks, s);
-        if (slot < 0)
-            return -1;
-        chacha_hp_kernel<<<1, 256, 0, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, (const ptls_mi355x_hp_t *)(d + 16), d, d + 64, 1,
-                                           (u32 *)(d + 80), token);
-        const hipError_t err = hipGetLastError();
-        (void)hipEventRecord(hp_ks->uses[slot].second, s);
-        return err == hipSuccess ? 0 : fail("chacha hp_mask launch: %s", hipGetErrorString(err));
+        return chacha_launch_noted(hp_ks, s, "chacha hp_mask launch: %s", [&] {
+            chacha_hp_kernel<<<1, 256, 0, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, (const ptls_mi355x_hp_t *)(d + 16), d, d + 64, 1,
+                                               (u32 *)(d + 80), token);
+        });
     }, 80, 1, token);
     if (ret != 0)
         return -1;

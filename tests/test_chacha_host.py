@@ -119,7 +119,17 @@ def test_contexts_reject_bad_sizes_before_any_device_call():
 def test_new_sources_enter_the_engine_digest():
     from picotls_amd import build as b
 
-    parts = {os.path.relpath(p, b.PKG) for p in b.ENGINE_PARTS}
-    on_disk = {os.path.join("csrc", "chacha", f) for f in os.listdir(os.path.join(b.PKG, "csrc", "chacha")) if f.endswith(".h")}
-    assert on_disk and on_disk <= parts
+    csrc = os.path.join(b.PKG, "csrc")
+    on_disk = {os.path.join(d, f) for d, _, files in os.walk(csrc) for f in files if f.endswith(".h")}
+    assert {os.path.join(csrc, "chacha", "host.h"), os.path.join(csrc, "host", "runtime.h"),
+            os.path.join(csrc, "engine", "common.h")} <= on_disk
+    assert on_disk <= set(b.ENGINE_PARTS)  # every header below csrc/, whatever its directory
     assert os.path.join(ROOT, "include", "picotls", "mi355x_chacha20.h") in b.HEADERS
+    # every quoted #include of the translation unit resolves to a file the digest covers
+    covered = {os.path.realpath(p) for p in b.ENGINE_SRCS + b.ENGINE_PARTS + b.HEADERS}
+    for src in b.ENGINE_SRCS + b.ENGINE_PARTS:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(src).read(), flags=re.M):
+            found = [p for p in (os.path.join(os.path.dirname(src), inc), os.path.join(csrc, inc), os.path.join(ROOT, "include", inc))
+                     if os.path.exists(p)]
+            assert found, f"{src} includes {inc}, which is not in the tree"
+            assert os.path.realpath(found[0]) in covered, f"{src} includes {inc}, which the engine digest does not cover"
