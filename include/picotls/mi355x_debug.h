@@ -14,8 +14,8 @@ extern "C" {
 /**
  * Counters since the last reset, into out[16]:
  *   out[0..4]  launches of the chunked batch kernel per instantiation: 0 plain (4-bit GHASH tables), 1 spread (small
- *              batch with long records), 2 seal with header-protection masks, 3 W8 butterfly end (long whole records
- *              of a W8 pair), 4 W8 serial end (every other run of a W8 pair)
+ *              batch with long records), 2 seal with header-protection masks, 3 W8 long whole records (the second
+ *              kernel of a W8 pair), 4 W8 serial (every other run of a W8 pair)
  *   out[5]     launches of the lockstep kernel, out[6] of the span kernels (a lone long record), out[7] 0
  *   out[8..12] runs processed on the device by each chunked instantiation (same order; a run skipped because the
  *              pair's other kernel takes it is not counted), out[13] 0, out[14] the EXT 4 runs among them that were

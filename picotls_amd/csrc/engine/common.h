@@ -133,11 +133,11 @@ __device__ __forceinline__ u32 lane_here()
 #define CLDS_ONE (CLDS_PART + 16 * CRUN_UNITS)                   // a lone record's descriptor (BatchArgs::one)
 #define CLDS_ALLOC (CLDS_ONE + 48)
 // W8 kernels (gcm_chunked_kernel EXT 3 and 4: the Horner step on an 8-bit H^8 table): every run of an unframed or
-// TLS-framed batch, EXT 4 with the serial lane-Horner segment end, EXT 3 (long whole records, W8_MIN_STEPS steps and
-// more) with the butterfly end. LDS map: AES [0, 64K), H^8 as an 8-bit window-major table over slots 0..7, H in slot 8
-// (window-major for EXT 4, nibble-major for EXT 3), the unit partials of at most W8_RUN_UNITS units at CLDS_PART
-// (their first 2 KiB the groups' E(K, J0) slots in whole runs; the table build's scratch before a run), at W8_TAB_COMB
-// the unit combine power (window-major, EXT 4) or H^2 (nibble-major, EXT 3)
+// TLS-framed batch, both with the serial lane-Horner segment end: EXT 4, and EXT 3 for long whole records
+// (W8_MIN_STEPS steps and more), whose waves are dealt records of one padding and issue in their own priority bands.
+// LDS map: AES [0, 64K), H^8 as an 8-bit window-major table over slots 0..7, H window-major in slot 8, the unit
+// partials of at most W8_RUN_UNITS units at CLDS_PART (their first 2 KiB the groups' E(K, J0) slots in whole runs; the
+// table build's scratch before a run), at W8_TAB_COMB the unit combine power (window-major, EXT 4)
 // (round 4: profiles/r4/w8_ab.txt, w8all_ab.txt.) TLS 1.2-framed batches take them too, although EXT 4's TLS 1.2 seal
 // spills 96 B per lane: 131072 x 16 KiB records 1036.9 -> 1172.1 GiB/s seal+open, 1M x 1200 B 907.2 -> 979.1
 // (tools/ab_tls12.py, profiles/r4/tls12_w8_ab.txt)

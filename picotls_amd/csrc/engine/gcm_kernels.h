@@ -832,17 +832,14 @@ __device__ __attribute__((noinline)) void spread_pieces(BatchArgs args, u32 w, u
 // partial region (free between runs) as the source of its 8-bit table over slots 0..7, H window-major into slot 8, and
 // (a cut run: usrc = the key element of its unit combine power) that power window-major at W8_TAB_COMB; then the 8-bit
 // table. Out of line: inlined into the run loop it cost the kernel's other runs registers (-4 % on 1200-byte records).
-// tree (the EXT 3 kernel: long whole records): H and H^2 nibble-major at W8_TAB_H and W8_TAB_COMB instead (w8_tree_end).
-__device__ __noinline__ void w8_build_tables(lds_u8 *lds, const lds_u8 *keyp, u32 usrc, bool tree, u32 hpow)
+__device__ __noinline__ void w8_build_tables(lds_u8 *lds, const lds_u8 *keyp, u32 usrc, u32 hpow)
 {
     typedef __attribute__((address_space(3))) const KeyEntry lds_key_t;
     lds_key_t *key = (lds_key_t *)keyp;
     auto el = [&](u32 i) { return u32x4{key->h[i][0], key->h[i][1], key->h[i][2], key->h[i][3]}; };
     build_elem_table(lds, CLDS_PART, el(hpow), 0, false);  // (the Horner power: H^8, or H^4 for 4-lane groups)
-    build_elem_table(lds, W8_TAB_H, el(0), 64, !tree);
-    if (tree)
-        build_elem_table(lds, W8_TAB_COMB, el(1), 128, false);
-    else if (usrc != 0xffffffffu)
+    build_elem_table(lds, W8_TAB_H, el(0), 64, true);
+    if (usrc != 0xffffffffu)
         build_elem_table(lds, W8_TAB_COMB, el(usrc), 128, true);
     __syncthreads();
     build_h8_byte_table(lds, CLDS_PART);
@@ -871,7 +868,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
     const u32 wave = threadIdx.x >> 6;
     const u32 tsel_horner = 0x10000u + (u32)(G - 1) * GHASH_TABLE_BYTES;
     constexpr bool W8K = EXT == 3 || EXT == 4 || EXT == 5;  // a W8 kernel (launch_chunked)
-    constexpr bool W8TREE = EXT == 3;                       // ... with the butterfly segment end
+    constexpr bool W8TREE = EXT == 3;                       // ... the pair's second: long whole records (named for its former butterfly end)
     // the unit combine table: slot 8, or in the W8 kernel's map W8_TAB_COMB
     const u32 tsel_chunk = W8K ? (u32)W8_TAB_COMB : 0x10000u + 8u * GHASH_TABLE_BYTES;
 
@@ -914,7 +911,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             beg = slist[0], end = slist[1];
     }
     u32 loaded_key = 0xffffffffu, loaded_usrc = 0xffffffffu;
-    u32 loaded_w8 = 0;  // the LDS holds the nine 4-bit tables (0) or the W8 map: serial segment ends (1), the tree (2)
+    u32 loaded_w8 = 0;  // the LDS holds the nine 4-bit tables (0) or the W8 map: for 8-lane groups (1), 4-lane (3), MK (4)
     // the descriptors in batch order, or (an ungrouped many-key batch) the key-grouped copy built on the device; ok
     // bytes go to the record's batch index either way
     const ptls_mi355x_record_t *recs = args.recs;
@@ -1067,12 +1064,13 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
         lds_key_t *key = (lds_key_t *)(rs + RUN_KEY_OFF);  // staged by the scanner
         // the EXT 3 kernel's runs (all W8: the others were skipped above) take the 8-bit Horner table (ghash.h)
         constexpr bool w8run = W8K;
-        // W8 segment ends: the serial chain (1), the tree (2), or a whole run of the serial kernel in 4-lane groups (3:
-        // Horner with H^4)
+        // W8 segment ends: the serial chain (1: EXT 3's long whole records too), or a whole run of the serial kernel in
+        // 4-lane groups (3: Horner with H^4)
         // (cut runs keep 8-lane groups: in 4-lane groups mixed measured -6 %, -18 % with units of half the length,
-        // profiles/r5/g4_ab.txt)
+        // profiles/r5/g4_ab.txt; so do EXT 3's long records: in 4-lane groups tls16k measured -0.8 % behind them,
+        // profiles/long_deal_ab.txt)
         const bool g4run = W8K && !W8TREE && whole;
-        const u32 w8mode = !w8run ? 0u : W8TREE ? 2u : g4run ? 3u : 1u;
+        const u32 w8mode = !w8run ? 0u : g4run ? 3u : 1u;
         const bool key_new = key_idx != loaded_key;
         if (mk_n != 0) {
             // (round 6) an MK run: each connection's H^4 and H as 4-bit window-major tables in its slot (ghash.h),
@@ -1090,9 +1088,8 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             loaded_usrc = 0xffffffffu;
             loaded_w8 = 4;
         } else if (w8run && (key_new || loaded_w8 != w8mode)) {
-            // the 8-bit H^8 (H^4) table over slots 0..7, H in slot 8, and a cut run's combine power (or the tree's H^2)
-            // at W8_TAB_COMB
-            w8_build_tables(lds, (const lds_u8 *)key, whole ? 0xffffffffu : usrc, w8mode == 2, w8mode == 3 ? 3u : 7u);
+            // the 8-bit H^8 (H^4) table over slots 0..7, H in slot 8, and a cut run's combine power at W8_TAB_COMB
+            w8_build_tables(lds, (const lds_u8 *)key, whole ? 0xffffffffu : usrc, w8mode == 3 ? 3u : 7u);
             loaded_key = key_idx;
             loaded_usrc = whole ? 0xffffffffu : usrc;
             loaded_w8 = w8mode;
@@ -1225,6 +1222,22 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                 k_back = f - (first - lo);
             }
         };
+        // The unit of group `slot` in the claim that starts at ub (a multiple of RPW). The EXT 3 kernel (whole runs of
+        // long records) deals each 64 units to its eight claims with a stride of RPW: claim c of the block takes units
+        // c, c + 8, ... c + 56. Packed records of one length whose outputs advance by 16 bytes modulo 128 (16 KiB TLS
+        // records and their tags) then share their front padding within a wave, where eight consecutive records hold
+        // all eight paddings: the wave runs its own records' steps and not the longest padding's (129 instead of 130
+        // for seven waves in eight), its lanes enter a counter window in the same step, and a wave whose records all
+        // start with an AAD-only step skips that step's AES (gcm_segment). Any other layout runs as it did: the
+        // segment takes every bound from the wave's lanes. A block's claims start at units block + c, increasing with
+        // ub, so the first claim whose first unit is past the run ends the loop as before.
+        auto claim_unit = [&](u32 ub, u32 slot) -> u32 {
+            if constexpr (W8TREE)
+                return (ub & ~63u) + ((ub >> 3) & 7u) + (u32)RPW * slot;
+            else
+                return ub + slot;
+        };
+        static_assert(RPW == 8, "claim_unit deals blocks of RPW * RPW units");
         bool g4done = false;
         if constexpr (W8K && !W8TREE) {
             if (g4run) {
@@ -1291,7 +1304,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             if (lane_here() == 0)
                 ub = atomicAdd((u32 *)&rs[RC_NEXT], (u32)RPW);
             ub = __builtin_amdgcn_readfirstlane(ub);
-            if (ub >= total_units) {
+            if (claim_unit(ub, 0) >= total_units) {  // (the claim's first unit: its others are further on)
                 if (with_hp && hp_n != 0) {  // the run's units are all handed out: masks of the previous run
                     u32 m = 0;
                     if (lane_here() == 0)
@@ -1308,7 +1321,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             u32 okw;
             {
                 const u32 lane = lane_here(), j = lane % G, slot = lane / G, laneoff = (lane & 31) * 4 | (W8K ? W8_AES_BASE : 0u);
-                const u32 u = ub + slot;
+                const u32 u = claim_unit(ub, slot);
                 const bool valid = u < total_units;
                 u32 lo, first, unc, k_back;
                 unit_of(valid ? u : 0u, lo, first, unc, k_back);
@@ -1342,7 +1355,7 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
             }
             // from here on everything is read again (run state, descriptor), not carried across the segment
             asm volatile("" ::: "memory");
-            const u32 lane = lane_here(), j = lane % G, u = ub + lane / G;
+            const u32 lane = lane_here(), j = lane % G, u = claim_unit(ub, lane / G);
             if (u >= total_units)
                 continue;  // (uniform over the group)
             u32 lo, first, unc, k_back;

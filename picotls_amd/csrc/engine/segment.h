@@ -396,8 +396,11 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         // the first step of 4-lane groups on short records) needs no keystream and skips the AES; the lengths decide
         // it, not the data
         const int lg = (int)(j + G * m0) - P;
-        // (4-lane groups only: in 8-lane kernels such a step is rare, and the test cost the TLS 1.3 open kernel spills)
-        const bool wave_ks = G != 4 || __any(m0 < m_hi && lg >= (int)na && lg <= (int)(na + nb)) != 0;
+        // (4-lane groups, and the 8-lane groups of the EXT 3 kernel's long whole records, w8tree: an aligned open of
+        // records with one AAD block starts every record with such a step, and so does the seal's wave whose records
+        // share that padding; in the other 8-lane kernels such a step is rare, and the test cost the TLS 1.3 open
+        // kernel spills, as it does EXT 3's TLS 1.2 seal: 16 bytes a lane)
+        const bool wave_ks = (G != 4 && !(w8tree && !TLS12)) || __any(m0 < m_hi && lg >= (int)na && lg <= (int)(na + nb)) != 0;
         u32 st[1][4];
         setup_step(m0, st, wave_ks);
         if (wave_ks)
@@ -440,12 +443,12 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         // sum over the group of a_l H^(e_l) (rank r = 8 - e owes H^(8 - r)): ((v_0 H + v_1) H + ... + v_7) H by eight
         // group multiplies with the one window-major table H (4 conflict-free lookups per lane each: 32, as
         // coop_last_powers, with one table instead of seven)
-        // (w8tree, the EXT 3 kernel's long whole records: the butterfly over the ranks with H and H^2 nibble-major)
+        // (the EXT 3 kernel's long whole records too: its butterfly over the ranks with H and H^2 nibble-major, 160
+        // lookups a lane for three short levels, measured behind this chain once its waves were dealt records of one
+        // padding and issued in priority bands -- tls16k -0.9 %, profiles/long_deal_ab.txt -- and is gone)
         const u32 rank = valid ? (u32)G - e_last : j;
         if constexpr (G == 4)
             acc = w8_lane_end4(lds, acc, lane_here(), rank, MK4 ? mk_htab(mk_kslot) : (u32)W8_TAB_H);
-        else if (w8tree)
-            acc = w8_tree_end(lds, acc, lane_here(), rank);
         else
             acc = w8_lane_end(lds, acc, lane_here(), rank);
         if (valid && m_hi * G >= N && j == jl)  // the segment holds the length block: E(K, J0), on its lane

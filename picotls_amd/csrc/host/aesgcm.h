@@ -569,7 +569,7 @@ static void launch_chunked(unsigned grid, hipStream_t s, const BatchArgs &a)
     }
     // The W8 kernels (the Horner step on an 8-bit H^8 table, ghash.h gmul8) for every run of an unframed or TLS-framed
     // batch: EXT 4 (segment ends by a serial lane Horner) takes all runs but those of long whole records, which EXT 3
-    // (the butterfly end: on 16 KiB records it measured 1 % above the serial one) takes after it, each skipping the
+    // (8-lane groups dealt records of one padding, its own priority bands, no code for cut runs) takes after it, each skipping the
     // other's runs and EXT 3 returning at once in the workgroups where EXT 4 saw none (BatchArgs::w8_split, w8_flags).
     // A batch of fewer than WHOLE_MIN_RECS records per workgroup in contiguous ranges holds no whole-record run: EXT 4
     // alone. Not for a per-record launch (it publishes completion words, and its 1-16-step units suit the 4-bit path),
