@@ -245,6 +245,24 @@ int ptls_mi355x_seal_batch_hp(ptls_mi355x_keyset_t *ks, const ptls_mi355x_record
                               void *masks, void *stream);
 
 /**
+ * QUIC packet protection, batched (RFC 9001 §5.3-5.4): the per-packet outcome of opening a batch of protected packets
+ * and its status codes. Suite-neutral; the calls that fill it are declared with their suite (the ChaCha20 form:
+ * ptls_mi355x_chacha_open_quic_packets, picotls/mi355x_chacha20.h).
+ */
+#define PTLS_MI355X_QUIC_OK 0
+#define PTLS_MI355X_QUIC_BAD_MAC 1
+#define PTLS_MI355X_QUIC_REJECTED 2  /* descriptor outside the call's limits; nothing written for it */
+#define PTLS_MI355X_QUIC_KEY_PHASE 3 /* short header whose key-phase bit differs from the expected one; not opened */
+typedef struct st_ptls_mi355x_quic_result_t { /* 16 bytes */
+    uint64_t pn;          /* full packet number (RFC 9000 A.3) */
+    uint32_t payload_len; /* plaintext bytes after the header */
+    uint8_t pn_len;       /* 1..4 */
+    uint8_t first_byte;   /* the first byte with protection removed (reserved bits and key phase are the stack's to judge) */
+    uint8_t status;       /* PTLS_MI355X_QUIC_* */
+    uint8_t reserved;
+} ptls_mi355x_quic_result_t;
+
+/**
  * QUIC-LB connection-ID encryption, batched (draft-ietf-quic-load-balancers; lib/quiclb-impl.h:100-162, the cipher
  * behind ptls_fusion_quiclb lib/fusion.c:2186-2233 / ptls_openssl_quiclb). Entry i transforms len bytes at
  * in + in_off into out + out_off (may alias) under the AES-128 key key_idx of ks (a keyset created with key_size 16;

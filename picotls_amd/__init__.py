@@ -12,7 +12,8 @@ operator interface (``include/picotls.h:519-580, 2082-2164``; ``lib/picotls.c:65
   :func:`seal_batch_hp`, :func:`quiclb_batch` -- the batch extension.
 * :class:`QuicLbCipher` -- mirror of ``ptls_mi355x_quiclb`` (fusion's ``ptls_fusion_quiclb``).
 * :class:`ChaChaKeyset`, :func:`chacha_seal_batch`, :func:`chacha_open_batch`, :func:`chacha_seal_tls_records`,
-  :func:`chacha_open_tls_records`, :func:`chacha_hp_mask_batch`, :data:`chacha20poly1305`, :class:`ChaChaCipher` -- the
+  :func:`chacha_open_tls_records`, :func:`chacha_hp_mask_batch`, :func:`chacha_seal_quic_packets`,
+  :func:`chacha_open_quic_packets`, :data:`chacha20poly1305`, :class:`ChaChaCipher` -- the
   ChaCha20-Poly1305 engine of ``include/picotls/mi355x_chacha20.h`` (``ptls_mi355x_chacha20poly1305`` / ``_chacha20``).
 
 There is no CPU fallback: when the shared object or a gfx950 device is missing every entry point raises.
@@ -25,8 +26,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .records import (CID_DTYPE, HP_DTYPE, QUICLB_MAX_LEN, QUICLB_MIN_LEN, RECORD_DTYPE, TLS_BAD_HEADER, TLS_BAD_MAC, TLS_OK, TLS_RESULT_DTYPE,  # noqa: F401
-                      TLS_UNEXPECTED_MESSAGE, RecordBatch, shard_ranges)
+from .records import (CID_DTYPE, HP_DTYPE, QUIC_BAD_MAC, QUIC_KEY_PHASE, QUIC_OK, QUIC_REJECTED, QUIC_RESULT_DTYPE, QUICLB_MAX_LEN,  # noqa: F401
+                      QUICLB_MIN_LEN, RECORD_DTYPE, TLS_BAD_HEADER, TLS_BAD_MAC, TLS_OK, TLS_RESULT_DTYPE, TLS_UNEXPECTED_MESSAGE,
+                      RecordBatch, shard_ranges)
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # PTLS_MI355X_LIB: another build of the same engine (an A/B variant under tools/variants/) for the GPU suite
@@ -93,6 +95,8 @@ CHACHA_ABI_FUNCTIONS = (
     "ptls_mi355x_chacha_seal_tls_records",
     "ptls_mi355x_chacha_open_tls_records",
     "ptls_mi355x_chacha_hp_mask_batch",
+    "ptls_mi355x_chacha_seal_quic_packets",
+    "ptls_mi355x_chacha_open_quic_packets",
     "ptls_mi355x_chacha_encrypt",
     "ptls_mi355x_chacha_encrypt_v",
     "ptls_mi355x_chacha_decrypt",
@@ -186,6 +190,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.ptls_mi355x_chacha_seal_tls_records.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.ptls_mi355x_chacha_open_tls_records.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.ptls_mi355x_chacha_hp_mask_batch.argtypes = [vp, vp, sz, vp, vp, vp]
+    lib.ptls_mi355x_chacha_seal_quic_packets.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    lib.ptls_mi355x_chacha_open_quic_packets.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     lib.ptls_mi355x_chacha_encrypt.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
     lib.ptls_mi355x_chacha_encrypt_v.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
     lib.ptls_mi355x_chacha_decrypt.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
@@ -454,6 +460,25 @@ def chacha_hp_mask_batch(hp_ks: ChaChaKeyset, hp_ptr: int, n: int, base_ptr: int
     """QUIC header-protection masks of the ChaCha20 suites (HP_DTYPE entries, 16 bytes per mask); device pointers."""
     if load_library().ptls_mi355x_chacha_hp_mask_batch(hp_ks.handle, hp_ptr, n, base_ptr, masks_ptr, stream or None) != 0:
         raise _err("ptls_mi355x_chacha_hp_mask_batch")
+
+
+def chacha_seal_quic_packets(ks: ChaChaKeyset, hp_ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int,
+                             stream: int = 0) -> None:
+    """QUIC packet protection (RFC 9001 5.3-5.4) in one launch: cleartext header || payload at in + in_off (aad_len header
+    bytes, len payload bytes, seq the full packet number) to protected header || ciphertext || tag; device pointers."""
+    if load_library().ptls_mi355x_chacha_seal_quic_packets(ks.handle, hp_ks.handle if hp_ks is not None else None, recs_ptr, nrecs,
+                                                           in_ptr, out_ptr, stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_seal_quic_packets")
+
+
+def chacha_open_quic_packets(ks: ChaChaKeyset, hp_ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int,
+                             ok_ptr: int, results_ptr: int, stream: int = 0) -> None:
+    """Removes header protection and opens protected QUIC packets (aad_len the packet-number offset, len the bytes from
+    there to the packet's end, seq the expected packet number, flags bit 0 the expected key phase): unprotected header ||
+    plaintext to out + out_off, QUIC_RESULT_DTYPE results (both ok and results are required); device pointers."""
+    if load_library().ptls_mi355x_chacha_open_quic_packets(ks.handle, hp_ks.handle if hp_ks is not None else None, recs_ptr, nrecs,
+                                                           in_ptr, out_ptr, ok_ptr or None, results_ptr or None, stream or None) != 0:
+        raise _err("ptls_mi355x_chacha_open_quic_packets")
 
 
 def chacha_debug_poly1305(key32: bytes, msg: bytes) -> bytes:

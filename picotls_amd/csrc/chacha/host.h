@@ -60,9 +60,13 @@ static unsigned chacha_grid(const DeviceState *ds, size_t nrecs)
 
 static void chacha_launch_kernel(bool open, int frame, unsigned grid, hipStream_t s, const ChaChaArgs &a)
 {
-    with_either<0, 1>(frame, [&](auto FRAME) {
+    const auto go = [&](auto FRAME) {
         with_bool(open, [&](auto OPEN) { chacha_batch_kernel<OPEN, FRAME><<<grid, CHACHA_WG, 0, s>>>(a); });
-    });
+    };
+    if (frame == 2)  // QUIC packets
+        go(std::integral_constant<int, 2>{});
+    else
+        with_either<0, 1>(frame, go);
 }
 
 static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int frame, const ptls_mi355x_record_t *recs, size_t nrecs,
@@ -84,6 +88,46 @@ static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int f
     a.claim = ks->d_claim + 2 * *slot;
     const unsigned grid = chacha_grid(ks->ds, nrecs);
     return chacha_launch_noted(ks, s, "chacha batch launch: %s", [&] { chacha_launch_kernel(open, frame, grid, s, a); });
+}
+
+// QUIC packets: one launch (seal), or the header pre-pass and the batch behind it on the same stream (open). The launch
+// reads both keysets, so it is a use of both: a free or rekey of either orders itself behind it. Two distinct keysets'
+// mutexes are taken in the order of their addresses, whichever role each has in this call.
+static int chacha_launch_quic(ptls_mi355x_chacha_keyset_t *ks, ptls_mi355x_chacha_keyset_t *hp_ks, bool open,
+                              const ptls_mi355x_record_t *recs, size_t nrecs, const void *in, void *out, uint8_t *ok,
+                              ptls_mi355x_quic_result_t *results, void *stream)
+{
+    if (ks == NULL || hp_ks == NULL ||
+        (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && (ok == NULL || results == NULL)))))
+        return fail("%s", "chacha quic packets: invalid arguments");
+    if (hp_ks->device != ks->device)
+        return fail("%s", "chacha quic packets: hp_ks is on another device than ks");
+    if (nrecs == 0)
+        return 0;
+    DeviceScope scope(ks->device);
+    hipStream_t s = (hipStream_t)stream;
+    const bool ks_first = std::less<ptls_mi355x_chacha_keyset_t *>()(ks, hp_ks);
+    std::unique_lock<std::mutex> lk1((ks_first ? ks : hp_ks)->mu), lk2;
+    if (hp_ks != ks)
+        lk2 = std::unique_lock<std::mutex>((ks_first ? hp_ks : ks)->mu);
+    const unsigned *slot = ks->slots.get(s, ks->uses, [&](unsigned &i) { return i = (unsigned)ks->slots.v.size(), true; });
+    if (slot == nullptr)
+        return -1;
+    ChaChaArgs a = {};
+    a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
+    a.recs = recs, a.nrecs = nrecs, a.in = (const uint8_t *)in, a.out = (uint8_t *)out, a.ok = ok;
+    a.claim = ks->d_claim + 2 * *slot;
+    a.hp_keys = hp_ks->d_keys, a.hp_nkeys = (u32)hp_ks->nkeys, a.results = results;
+    const unsigned grid = chacha_grid(ks->ds, nrecs);
+    const auto launch = [&] {
+        return chacha_launch_noted(ks, s, "chacha quic packets launch: %s", [&] {
+            if (open)
+                chacha_quic_unmask_kernel<<<aux_grid(nrecs, ks->ds->ncu), 256, 0, s>>>(a.hp_keys, a.hp_nkeys, a.nkeys, recs, nrecs, a.in,
+                                                                                     results);
+            chacha_launch_kernel(open, 2, grid, s, a);
+        });
+    };
+    return hp_ks != ks ? launch_and_note(hp_ks->uses, hp_ks->ds, s, launch) : launch();
 }
 
 extern "C" {
@@ -239,6 +283,19 @@ int ptls_mi355x_chacha_open_tls_records(ptls_mi355x_chacha_keyset_t *ks, const p
                                                                                      (const uint8_t *)out, ok, results);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+int ptls_mi355x_chacha_seal_quic_packets(ptls_mi355x_chacha_keyset_t *ks, ptls_mi355x_chacha_keyset_t *hp_ks,
+                                         const ptls_mi355x_record_t *recs, size_t nrecs, const void *in, void *out, void *stream)
+{
+    return chacha_launch_quic(ks, hp_ks, false, recs, nrecs, in, out, NULL, NULL, stream);
+}
+
+int ptls_mi355x_chacha_open_quic_packets(ptls_mi355x_chacha_keyset_t *ks, ptls_mi355x_chacha_keyset_t *hp_ks,
+                                         const ptls_mi355x_record_t *recs, size_t nrecs, const void *in, void *out, uint8_t *ok,
+                                         ptls_mi355x_quic_result_t *results, void *stream)
+{
+    return chacha_launch_quic(ks, hp_ks, true, recs, nrecs, in, out, ok, results, stream);
 }
 
 int ptls_mi355x_chacha_hp_mask_batch(ptls_mi355x_chacha_keyset_t *hp_ks, const ptls_mi355x_hp_t *hp, size_t n, const void *base,

@@ -17,6 +17,11 @@
 // partial with the position of the length block; the partials are added across the group, the length block is added
 // and one multiplication by r, one reduction mod 2^130 - 5 and the addition of s finish the tag. r^(4G - 3) and r^E come
 // from log2(4G) - 1 squarings of r per record.
+//
+// Framing. FRAME 0: ciphertext || tag, the AAD from its own arena. FRAME 1: TLS 1.3 wire records. FRAME 2: QUIC packets
+// (RFC 9001 §5.3-5.4): the header in front of the text is the AAD; seal also runs the header-protection
+// block on the sample out of text block 0 and masks the header, open takes packet number and lengths from the
+// results of chacha_quic_unmask_kernel, launched ahead of it, and writes the unprotected header.
 #ifndef PTLS_MI355X_CHACHA_KERNELS_H
 #define PTLS_MI355X_CHACHA_KERNELS_H
 
@@ -39,12 +44,38 @@ struct ChaChaArgs {
     unsigned long long *claim;
     u32 *done_flag;  // per-record path: one completion word per workgroup (publish_done)
     u32 done_token;
+    // QUIC packets (FRAME 2): the header-protection keys, and the pre-pass's results that the open reads and completes
+    u32 hp_nkeys;
+    const ChaChaKey *hp_keys;
+    ptls_mi355x_quic_result_t *results;
 };
 
 // launches per group width (ptls_mi355x_chacha_debug_counters): [0] narrow, [1] wide, counted by workgroup 0
 __device__ unsigned long long g_chacha_launches[2];
 
 __device__ __forceinline__ u32 sub_clamp16(u32 n, u32 off) { return n > off ? min(n - off, 16u) : 0u; }
+
+// QUIC seal (RFC 9001 §5.4.1): the mask of `sample` under the packet's header-protection key (the block of
+// chacha_hp_kernel) onto the header at out + out_off, which holds the cleartext header already: the first byte takes
+// mask[0] & 0x1f (short header) or & 0x0f (long), packet-number byte i takes mask[1 + i].
+__device__ __forceinline__ void quic_protect_header(const ChaChaArgs &a, const ptls_mi355x_record_t &r, u32 first, u32 pn_len,
+                                                    u32x4 sample)
+{
+    const ChaChaKey *hk = a.hp_keys + r.key_idx;
+    const u32x4 k0 = *(const u32x4 *)&hk->key[0], k1 = *(const u32x4 *)&hk->key[4];
+    const u32 key[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
+    u32 x[16];
+    chacha20_block(key, sample.x, sample.y, sample.z, sample.w, x);
+    const uint8_t *pin = a.in + r.in_off + r.aad_len - pn_len;
+    uint8_t *hout = a.out + r.out_off, *pout = hout + r.aad_len - pn_len;
+    const u32 m14 = x[0] >> 8 | x[1] << 24;  // mask[1 .. 4]
+    hout[0] = (uint8_t)(first ^ (x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu)));
+#pragma unroll
+    for (u32 i = 0; i < 4; ++i) {
+        if (i < pn_len)
+            pout[i] = (uint8_t)(pin[i] ^ (m14 >> (8 * i)));
+    }
+}
 
 template <int G, bool OPEN, int FRAME>
 __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 j)
@@ -56,11 +87,34 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
     ptls_mi355x_record_t r = {};
     if (valid)
         r = a.recs[idx];
-    const u32 A = FRAME ? (u32)TLS_HEADER_SIZE : PTLS_MI355X_RECORD_AAD_LEN(&r);
-    const u32 T = r.len + (FRAME && !OPEN ? 1u : 0u);  // text bytes (TLS seal: the payload and the inner content type)
+    // QUIC packets: the packet-number length, the first byte in the clear and the full packet number (seal: r.seq as
+    // given; open: what the pre-pass reconstructed, with the payload length and its verdict, in results[idx])
+    [[maybe_unused]] u32 pn_len = 0, first = 0, quic_len = 0;
+    [[maybe_unused]] bool quic_good = false;
+    if constexpr (FRAME == 2) {
+        if constexpr (OPEN) {
+            u32x4 q = {0, 0, 0, (u32)PTLS_MI355X_QUIC_REJECTED << 16};
+            if (valid)
+                q = *(const u32x4_u *)(a.results + idx);
+            r.seq = (u64)q.x | (u64)q.y << 32, quic_len = q.z, pn_len = q.w & 0xff, first = (q.w >> 8) & 0xff;
+            quic_good = valid && ((q.w >> 16) & 0xff) == PTLS_MI355X_QUIC_OK;
+        } else {
+            quic_good = valid && r.aad_len >= 2 && r.flags == 0 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.key_idx < a.nkeys &&
+                        r.key_idx < a.hp_nkeys;
+            if (quic_good)
+                first = a.in[r.in_off];
+            pn_len = (first & 3) + 1, quic_len = r.len;
+            // the header holds a byte before the packet number, and packet number and payload cover a sample's first 4 bytes
+            quic_good = quic_good && r.aad_len >= 1 + pn_len && pn_len + r.len >= 4;
+        }
+    }
+    const u32 A = FRAME == 1 ? (u32)TLS_HEADER_SIZE : FRAME == 2 ? r.aad_len + (OPEN ? pn_len : 0u) : PTLS_MI355X_RECORD_AAD_LEN(&r);
+    // text bytes (TLS seal: the payload and the inner content type)
+    const u32 T = FRAME == 2 ? quic_len : r.len + (FRAME == 1 && !OPEN ? 1u : 0u);
     // a descriptor beyond the limits is rejected: nothing is written for it and open reports ok = 0
-    const bool good = valid && r.len <= PTLS_MI355X_MAX_RECORD_LEN && A <= PTLS_MI355X_MAX_AAD_LEN && r.key_idx < a.nkeys &&
-                      (FRAME == 0 || OPEN || r.len <= CHACHA_TLS_MAX_PLAIN) && (FRAME != 0 || A == 0 || a.aad != nullptr);
+    const bool good = FRAME == 2 ? quic_good && r.key_idx < a.nkeys
+                                 : valid && r.len <= PTLS_MI355X_MAX_RECORD_LEN && A <= PTLS_MI355X_MAX_AAD_LEN && r.key_idx < a.nkeys &&
+                                       (FRAME == 0 || OPEN || r.len <= CHACHA_TLS_MAX_PLAIN) && (FRAME != 0 || A == 0 || a.aad != nullptr);
     const ChaChaKey *ke = a.keys + (good ? r.key_idx : 0);
     u32 key[8];
     {
@@ -70,8 +124,8 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
     }
     // nonce = static IV ^ (0^32 || BE64(seq))
     const u32 n0 = ke->iv[0], n1 = ke->iv[1] ^ bswap32((u32)(r.seq >> 32)), n2 = ke->iv[2] ^ bswap32((u32)r.seq);
-    const uint8_t *src = a.in + r.in_off + (FRAME && OPEN ? TLS_HEADER_SIZE : 0);
-    uint8_t *dst = a.out + r.out_off + (FRAME && !OPEN ? TLS_HEADER_SIZE : 0);
+    const uint8_t *src = a.in + r.in_off + (FRAME == 2 ? A : FRAME && OPEN ? TLS_HEADER_SIZE : 0);
+    uint8_t *dst = a.out + r.out_off + (FRAME == 2 ? A : FRAME && !OPEN ? TLS_HEADER_SIZE : 0);
     const u32 Cb = (T + 63) >> 6, C = (T + 15) >> 4;  // 64-byte blocks, 16-byte blocks of the text
 
     // the lane's first block: counter j (lane 0: the Poly1305 key block, whose r and s go to the whole group)
@@ -101,10 +155,12 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
     }
 
     Fe h = fe_zero();
-    // one 64-byte block b of the text, keystream in x: crypt it, then fold its 16-byte blocks into h
-    auto text_block = [&](u32 b) {
+    [[maybe_unused]] u32x4 sample = {0, 0, 0, 0};  // QUIC seal, lane 1: the header-protection sample out of text block 0
+    // one 64-byte block b of the text, keystream in x: crypt it, then fold its 16-byte blocks into h (FIRST: the call
+    // for the lane's first block, the only one that can be text block 0)
+    auto text_block = [&](u32 b, auto FIRST) {
         const u32 o = 64 * b, nT = min(64u, T - o);
-        const u32 nS = FRAME && !OPEN ? (r.len > o ? min(64u, r.len - o) : 0u) : nT;  // bytes the input holds
+        const u32 nS = FRAME == 1 && !OPEN ? (r.len > o ? min(64u, r.len - o) : 0u) : nT;  // bytes the input holds
         u32x4 c[4];
         if (nT == 64 && nS == 64) {  // a whole block: four 16-byte accesses, nothing to clamp or mask
 #pragma unroll
@@ -120,7 +176,7 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
         for (u32 w = 0; w < 4; ++w) {
             const u32 ns = sub_clamp16(nS, 16 * w), nt = sub_clamp16(nT, 16 * w);
             u32x4 p = load_upto16(src + o + 16 * w, ns);
-            if (FRAME && !OPEN && r.len - o - 16 * w < 16) {  // the inner content type follows the payload
+            if (FRAME == 1 && !OPEN && r.len - o - 16 * w < 16) {  // the inner content type follows the payload
                 const u32 at = r.len - o - 16 * w, t = (u32)(r.flags & 0xff) << (8 * (at & 3));
 #pragma unroll
                 for (u32 k = 0; k < 4; ++k)
@@ -130,6 +186,12 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
             const u32x4 q = p ^ ks;
             store_upto16(dst + o + 16 * w, q, nt);
             c[w] = OPEN ? p : keep_bytes(q, nt);  // the ciphertext, zero from its end
+        }
+        if constexpr (FRAME == 2 && !OPEN && decltype(FIRST)::value) {
+            // the 16 ciphertext bytes from 4 - pn_len (used when they all exist: T >= 20 - pn_len)
+            const u32 s = 4 - pn_len;
+            sample.x = __builtin_amdgcn_alignbyte(c[0].y, c[0].x, s), sample.y = __builtin_amdgcn_alignbyte(c[0].z, c[0].y, s);
+            sample.z = __builtin_amdgcn_alignbyte(c[0].w, c[0].z, s), sample.w = __builtin_amdgcn_alignbyte(c[1].x, c[0].w, s);
         }
         const u32 nb = (nT + 15) >> 4;
         if (nb == 4 && b + G < Cb) {
@@ -150,7 +212,42 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
 
     if (good) {
         if (j == 1) {  // the owner of text block 0 starts with the AAD
-            if (FRAME) {
+            if constexpr (FRAME == 2) {
+                // the header, 16 bytes at a time: the AAD is the header in the clear, which is also what open writes
+                // out; seal copies it out as it is and masks its first byte and packet number once the sample exists
+                const uint8_t *hin = a.in + r.in_off;
+                uint8_t *hout = a.out + r.out_off;
+                for (u32 off = 0; off < A; off += 16) {
+                    // The text follows the header in both arenas, so where 16 bytes from here still lie inside header
+                    // and text the header's last block is one access each way instead of a byte loop: the text bytes
+                    // it carries go out as they came in, into the start of text block 0, which this lane writes (or,
+                    // in place, reads: the same bytes) after this.
+                    const u32 n = min(16u, A - off);
+                    const bool whole = off + 16 <= A + T;
+                    u32x4 w = whole ? *(const u32x4_u *)(hin + off) : load_upto16(hin + off, n);
+                    if (OPEN) {
+                        if (off == 0)
+                            w.x = (w.x & ~0xffu) | first;
+                        if (off + 16 > r.aad_len) {  // packet-number bytes in this block (they may straddle two)
+#pragma unroll
+                            for (u32 i = 0; i < 4; ++i) {
+                                const u32 at = r.aad_len + i - off;  // (wraps for a byte of an earlier block)
+                                if (i < pn_len && at < 16) {
+                                    const u32 sh = 8 * (at & 3), v = ((u32)r.seq >> (8 * (pn_len - 1 - i))) & 0xff;
+#pragma unroll
+                                    for (u32 k = 0; k < 4; ++k)
+                                        w[k] = (at >> 2) == k ? (w[k] & ~(0xffu << sh)) | v << sh : w[k];
+                                }
+                            }
+                        }
+                    }
+                    if (whole)
+                        *(u32x4_u *)(hout + off) = w, w = keep_bytes(w, n);
+                    else
+                        store_upto16(hout + off, w, n);
+                    fe_add_block(h, w.x, w.y, w.z, w.w, 1), h = fe_mul(h, r1);
+                }
+            } else if (FRAME) {
                 u32 w0, w1;
                 if (OPEN) {  // the header as received
                     const uint8_t *hp = a.in + r.in_off;
@@ -171,10 +268,17 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
             }
         }
         if (j >= 1 && j - 1 < Cb)
-            text_block(j - 1);
+            text_block(j - 1, std::true_type{});
+        if constexpr (FRAME == 2 && !OPEN) {
+            // The sample lies in text block 0, which this lane holds: the one block under the header-protection key
+            // here, before the lane's other blocks. (No lane has a block to spare at 1200 bytes and four lanes, 20
+            // blocks, so the owner of the ciphertext takes it and nothing crosses lanes.)
+            if (j == 1 && T + pn_len >= 20)
+                quic_protect_header(a, r, first, pn_len, sample);
+        }
         for (u32 v = j + G; v <= Cb; v += G) {
             chacha20_block(key, v, n0, n1, n2, x);
-            text_block(v - 1);
+            text_block(v - 1, std::false_type{});
         }
     }
 
@@ -185,6 +289,7 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
         for (int m = 1; m < G; m <<= 1)
             h.v[i] += (u32)__shfl_xor((int)h.v[i], m, G);
     }
+    [[maybe_unused]] u32x4 qtag = {0, 0, 0, 0};  // QUIC seal: the tag, for a sample that reaches into it
     if (good && j == 0) {
         fe_add_block(h, A, 0, T, 0, 1);  // LE64(aadlen) || LE64(textlen)
         h = fe_mul(h, r1);
@@ -195,12 +300,46 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
             const u32x4 got = *(const u32x4_u *)(src + T);
             const u32 diff = (got.x ^ tag[0]) | (got.y ^ tag[1]) | (got.z ^ tag[2]) | (got.w ^ tag[3]);
             a.ok[idx] = diff == 0;
+            if constexpr (FRAME == 2)  // (the other fields stay as the pre-pass wrote them)
+                ((uint8_t *)(a.results + idx))[offsetof(ptls_mi355x_quic_result_t, status)] =
+                    diff == 0 ? PTLS_MI355X_QUIC_OK : PTLS_MI355X_QUIC_BAD_MAC;
         } else {
             const u32x4 t = {tag[0], tag[1], tag[2], tag[3]};
             *(u32x4_u *)(dst + T) = t;
+            if constexpr (FRAME == 2)
+                qtag = t;
         }
     } else if (OPEN && valid && j == 0) {
-        a.ok[idx] = 0;
+        a.ok[idx] = 0;  // (a QUIC packet the pre-pass did not pass keeps the status it gave)
+    }
+    if constexpr (FRAME == 2 && !OPEN) {
+        // The rare packet of under 20 - pn_len payload bytes: its sample ends in the tag. Lane 1, which wrote the header
+        // and the ciphertext, reads its own (at most 18) ciphertext bytes back, takes the tag from lane 0 and finishes
+        // the header: every byte involved is stored by the lane that reads it, and the common arm above keeps nothing
+        // in registers for this one.
+        const bool late = good && T + pn_len < 20;
+        if (__any(late)) {  // (the same in every lane of the wave)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                qtag[k] = (u32)__shfl((int)qtag[k], 0, G);
+            if (late && j == 1) {
+                const u32x4 c = load_upto16(dst, min(T, 16u));
+                const u32 c4 = (T > 16 ? (u32)dst[16] : 0u) | (T > 17 ? (u32)dst[17] << 8 : 0u);
+                const u32 s = 4 - pn_len, nc = T - s;  // nc (0 .. 15) ciphertext bytes from s, then the tag
+                u64 lo = (u64)__builtin_amdgcn_alignbyte(c.y, c.x, s) | (u64)__builtin_amdgcn_alignbyte(c.z, c.y, s) << 32;
+                u64 hi = (u64)__builtin_amdgcn_alignbyte(c.w, c.z, s) | (u64)__builtin_amdgcn_alignbyte(c4, c.w, s) << 32;
+                u64 tlo = (u64)qtag.x | (u64)qtag.y << 32, thi = (u64)qtag.z | (u64)qtag.w << 32;
+                if (nc >= 8)
+                    thi = tlo, tlo = 0;
+                if ((nc & 7) != 0) {
+                    thi = thi << (8 * (nc & 7)) | tlo >> (64 - 8 * (nc & 7));
+                    tlo <<= 8 * (nc & 7);
+                }
+                lo |= tlo, hi |= thi;
+                const u32x4 smp = {(u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32)};
+                quic_protect_header(a, r, first, pn_len, smp);
+            }
+        }
     }
 }
 
@@ -314,6 +453,51 @@ __global__ __launch_bounds__(256) void chacha_hp_kernel(const ChaChaKey *keys, u
         *(u32x4_u *)(masks + 16 * i) = m;
     }
     publish_done(done_flag, done_token);
+}
+
+// The pre-pass of ptls_mi355x_chacha_open_quic_packets (RFC 9001 §5.4.2, RFC 9000 A.3), one lane per packet in the shape
+// of chacha_hp_kernel: the mask from the sample 4 bytes behind the packet-number offset, the first byte and the packet
+// number unmasked, the full packet number from the expected one, the rejections and the key-phase verdict, all into
+// results[i], which the FRAME 2 open of chacha_batch_kernel reads for its nonce and lengths. Nothing else is written.
+__global__ __launch_bounds__(256) void chacha_quic_unmask_kernel(const ChaChaKey *hp_keys, u32 hp_nkeys, u32 nkeys,
+                                                                 const ptls_mi355x_record_t *recs, u64 n, const uint8_t *in,
+                                                                 ptls_mi355x_quic_result_t *results)
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const ptls_mi355x_record_t r = recs[i];
+        u32x4 res = {0, 0, 0, (u32)PTLS_MI355X_QUIC_REJECTED << 16};
+        // len: the packet number, the ciphertext and the tag; 4 + 16 of them are the sample's bytes at the least
+        if (r.len >= 20 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.aad_len >= 1 && r.key_idx < nkeys && r.key_idx < hp_nkeys) {
+            const uint8_t *p = in + r.in_off, *pn = p + r.aad_len;
+            const u32x4 s = *(const u32x4_u *)(pn + 4);
+            const ChaChaKey *ke = hp_keys + r.key_idx;
+            u32 key[8], x[16];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                key[k] = ke->key[k];
+            chacha20_block(key, s.x, s.y, s.z, s.w, x);
+            u32 first = p[0];
+            first ^= x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu);
+            const u32 pn_len = (first & 3) + 1, m14 = x[0] >> 8 | x[1] << 24;  // mask[1 .. 4]
+            u32 trunc = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) {
+                if (k < pn_len)
+                    trunc = trunc << 8 | (((u32)pn[k] ^ (m14 >> (8 * k))) & 0xff);
+            }
+            // RFC 9000 A.3: the candidate in the expected number's window, moved a window up or down when that is closer
+            const u64 win = 1ull << (8 * pn_len), hwin = win >> 1;
+            u64 cand = (r.seq & ~(win - 1)) | trunc;
+            if (cand + hwin <= r.seq && cand < (1ull << 62) - win)
+                cand += win;
+            else if (cand > r.seq + hwin && cand >= win)
+                cand -= win;
+            const bool phase = (first & 0x80) == 0 && ((first >> 2) & 1) != (r.flags & 1u);
+            res.x = (u32)cand, res.y = (u32)(cand >> 32), res.z = r.len - pn_len - 16;
+            res.w = pn_len | first << 8 | (u32)(phase ? PTLS_MI355X_QUIC_KEY_PHASE : PTLS_MI355X_QUIC_OK) << 16;
+        }
+        *(u32x4_u *)(results + i) = res;
+    }
 }
 
 // rekey (ptls_mi355x_chacha_keyset_update): entry idx[i] = src[i]

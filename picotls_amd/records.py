@@ -39,6 +39,12 @@ TLS_RESULT_DTYPE = np.dtype([("plain_len", "<u4"), ("content_type", "u1"), ("sta
 assert TLS_RESULT_DTYPE.itemsize == 8
 TLS_OK, TLS_BAD_MAC, TLS_BAD_HEADER, TLS_UNEXPECTED_MESSAGE = 0, 1, 2, 3
 
+# ptls_mi355x_quic_result_t: per-packet outcome of the open_quic_packets calls (PTLS_MI355X_QUIC_* statuses)
+QUIC_RESULT_DTYPE = np.dtype([("pn", "<u8"), ("payload_len", "<u4"), ("pn_len", "u1"), ("first_byte", "u1"), ("status", "u1"),
+                              ("reserved", "u1")])
+assert QUIC_RESULT_DTYPE.itemsize == 16
+QUIC_OK, QUIC_BAD_MAC, QUIC_REJECTED, QUIC_KEY_PHASE = 0, 1, 2, 3
+
 
 def _round16(x):
     if isinstance(x, np.ndarray):
