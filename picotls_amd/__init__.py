@@ -9,7 +9,8 @@ operator interface (``include/picotls.h:519-580, 2082-2164``; ``lib/picotls.c:65
 * :func:`aead_new_direct` / :func:`aead_new` (traffic secret -> key, IV) -> :class:`AeadContext` with ``encrypt`` / ``encrypt_s`` / ``decrypt`` / ``get_iv`` /
   ``set_iv`` / ``xor_iv`` (``decrypt`` returns ``None`` where picotls returns ``SIZE_MAX``)
 * :class:`Keyset`, :func:`seal_batch`, :func:`open_batch`, :func:`ecb_batch`, :func:`hp_mask_batch`,
-  :func:`seal_batch_hp`, :func:`quiclb_batch` -- the batch extension.
+  :func:`seal_batch_hp`, :func:`seal_quic_packets`, :func:`open_quic_packets`, :func:`quiclb_batch` -- the batch
+  extension.
 * :class:`QuicLbCipher` -- mirror of ``ptls_mi355x_quiclb`` (fusion's ``ptls_fusion_quiclb``).
 * :class:`ChaChaKeyset`, :func:`chacha_seal_batch`, :func:`chacha_open_batch`, :func:`chacha_seal_tls_records`,
   :func:`chacha_open_tls_records`, :func:`chacha_hp_mask_batch`, :func:`chacha_seal_quic_packets`,
@@ -70,6 +71,11 @@ ABI_FUNCTIONS = (
     "ptls_mi355x_staging_bytes",
     "ptls_mi355x_release_staging",
     "ptls_mi355x_last_error",
+)
+# every function of include/picotls/mi355x_quic.h: QUIC packet protection under AES-GCM (same shared object)
+QUIC_ABI_FUNCTIONS = (
+    "ptls_mi355x_seal_quic_packets",
+    "ptls_mi355x_open_quic_packets",
 )
 # include/picotls/mi355x_debug.h: test and measurement hooks (not the picotls boundary)
 DEBUG_FUNCTIONS = (
@@ -158,6 +164,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.ptls_mi355x_seal_tls12_records.argtypes = [vp, vp, sz, vp, vp, vp]
     lib.ptls_mi355x_open_tls12_records.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     lib.ptls_mi355x_seal_batch_hp.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.ptls_mi355x_seal_quic_packets.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    lib.ptls_mi355x_open_quic_packets.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
     lib.ptls_mi355x_encrypt.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
     lib.ptls_mi355x_encrypt_v.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
     lib.ptls_mi355x_encrypt_s.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz, vp, sz, sz, vp]
@@ -364,6 +372,27 @@ def seal_batch_hp(ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, aad_ptr: i
     if load_library().ptls_mi355x_seal_batch_hp(ks.handle, recs_ptr, nrecs, in_ptr, aad_ptr or None, out_ptr, hp_ks.handle,
                                                 hp_ptr, masks_ptr, stream or None) != 0:
         raise _err("ptls_mi355x_seal_batch_hp")
+
+
+def seal_quic_packets(ks: Keyset, hp_ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, stream: int = 0) -> None:
+    """QUIC packet protection under AES-GCM (RFC 9001 5.3-5.4) in one call: cleartext header || payload at in + in_off
+    (aad_len header bytes, len payload bytes, seq the full packet number) to protected header || ciphertext || tag at
+    out + out_off, the mask AES-ECB(hp_ks key, sample); device pointers."""
+    if load_library().ptls_mi355x_seal_quic_packets(ks.handle if ks is not None else None, hp_ks.handle if hp_ks is not None else None,
+                                                    recs_ptr, nrecs, in_ptr, out_ptr, stream or None) != 0:
+        raise _err("ptls_mi355x_seal_quic_packets")
+
+
+def open_quic_packets(ks: Keyset, hp_ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, ok_ptr: int,
+                      results_ptr: int, stream: int = 0) -> None:
+    """Removes header protection and opens protected QUIC packets under AES-GCM (aad_len the packet-number offset, len
+    the bytes from there to the packet's end, seq the expected packet number, flags bit 0 the expected key phase):
+    unprotected header || plaintext to out + out_off, QUIC_RESULT_DTYPE results (both ok and results are required);
+    device pointers."""
+    if load_library().ptls_mi355x_open_quic_packets(ks.handle if ks is not None else None, hp_ks.handle if hp_ks is not None else None,
+                                                    recs_ptr, nrecs, in_ptr, out_ptr, ok_ptr or None, results_ptr or None,
+                                                    stream or None) != 0:
+        raise _err("ptls_mi355x_open_quic_packets")
 
 
 def quiclb_batch(ks: Keyset, cids_ptr: int, n: int, in_ptr: int, out_ptr: int, stream: int = 0) -> None:

@@ -25,7 +25,7 @@ ENGINE_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 ENGINE_SRCS = [os.path.join(PKG, "csrc", "aesgcm_engine.hip")]
 PICOTLS_SRCS = [os.path.join(PKG, "csrc", "ptls_mi355x.c"), os.path.join(PKG, "csrc", "ptls_mi355x_chacha20.c")]
 HEADERS = [os.path.join(ROOT, "include", "picotls", h) for h in ("mi355x.h", "mi355x_picotls.h", "mi355x_debug.h",
-                                                                  "mi355x_chacha20.h", "mi355x_chacha20_picotls.h")]
+                                                                  "mi355x_chacha20.h", "mi355x_chacha20_picotls.h", "mi355x_quic.h")]
 # included by aesgcm_engine.hip (one translation unit): every header in every directory below csrc/, listed from disk so
 # that a new directory enters the digest by existing (engine/ device code, host/ the shared host layer, chacha/)
 ENGINE_PARTS = sorted(os.path.join(d, f) for d, _, files in os.walk(os.path.join(PKG, "csrc"))

@@ -44,6 +44,7 @@
 
 #include "picotls/mi355x.h"
 #include "picotls/mi355x_debug.h"
+#include "picotls/mi355x_quic.h"
 
 // Device code, in dependency order (one translation unit: the kernels are templates instantiated by the host side)
 #include "engine/common.h"

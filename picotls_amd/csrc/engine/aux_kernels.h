@@ -263,6 +263,191 @@ __global__ __launch_bounds__(256) void hp_kernel(const KeyEntry *keys, u32 nkeys
     publish_done(done_flag, done_token);  // (the per-record path: see gcm_chunked_kernel)
 }
 
+// ------------------------------------------------------------------------------------------------ QUIC packets
+// ptls_mi355x_seal_quic_packets / ptls_mi355x_open_quic_packets (RFC 9001 §5.3-5.4): the FRAME 3 batch kernel between a
+// pre-pass and a finish kernel, one lane per packet each, all on the call's stream. The pre-pass judges the caller's
+// descriptor and writes the one the batch kernel walks (keyset scratch): in_off, out_off and key_idx as given, the
+// whole header's length as the AAD length (aad_len | flags << 16), the GCM text's length, the full packet number. A
+// packet that did not pass keeps its key_idx (its connection's key run stays one run) and gets a len that record_ok
+// refuses, so the batch kernel writes nothing for it and an open gives ok = 0.
+// The two kernels that compute masks hold the AES T-tables in LDS (64 KiB a workgroup, two workgroups a CU): workgroups of
+// QUIC_AUX_WG threads, so that a CU has 2048 lanes' loads in flight (profiles/aesgcm_quic.md: with hp_kernel's 256 the
+// scattered header and sample loads of 512 lanes a CU were the launches' time).
+#define QUIC_AUX_WG 1024
+#define QUIC_DESC_REFUSED 0xffffffffu
+static_assert(QUIC_DESC_REFUSED > PTLS_MI355X_MAX_RECORD_LEN, "record_ok refuses the len of a packet that did not pass");
+
+__device__ __forceinline__ void quic_put_desc(ptls_mi355x_record_t *desc, const ptls_mi355x_record_t &r, bool pass, u32 A, u32 len, u64 seq)
+{
+    ptls_mi355x_record_t d = {};
+    d.in_off = r.in_off, d.out_off = r.out_off, d.seq = seq, d.key_idx = r.key_idx;
+    d.len = pass ? len : QUIC_DESC_REFUSED;
+    d.aad_len = pass ? (uint16_t)A : (uint16_t)0, d.flags = pass ? (uint16_t)(A >> 16) : (uint16_t)0;
+    *desc = d;
+}
+
+// AES-ECB(hp key, sample): the header-protection mask (hp_kernel's block)
+template <int NR>
+__device__ __forceinline__ u32x4 quic_mask(const lds_u8 *lds, u32 laneoff, const KeyEntry *k, u32x4 v)
+{
+    u32 rk[NR + 1][4];
+    for (int r = 0; r <= NR; ++r)
+        for (int c = 0; c < 4; ++c)
+            rk[r][c] = k->rk[r][c];
+    u32 s0 = v[0] ^ rk[0][0], s1 = v[1] ^ rk[0][1], s2 = v[2] ^ rk[0][2], s3 = v[3] ^ rk[0][3];
+    aes_encrypt_tt<NR>(lds, laneoff, rk, s0, s1, s2, s3);
+    return u32x4{s0, s1, s2, s3};
+}
+
+// byte `pos` (0..15) of v ^= b, without indexing the vector by a run-time value
+__device__ __forceinline__ u32x4 quic_xor_byte(u32x4 v, u32 pos, u32 b)
+{
+    const u32 w = (b & 0xffu) << (8 * (pos & 3));
+#pragma unroll
+    for (u32 c = 0; c < 4; ++c)
+        v[c] ^= (pos >> 2) == c ? w : 0u;
+    return v;
+}
+
+// the A header bytes of a packet from src to dst (the same address in place) with the first byte XORed with fmask
+// (mask[0] & 0x1f or & 0x0f) and the pn_len packet-number bytes at its end with m14 = mask[1 .. 4]. The masks go onto
+// the bytes in registers: a header of up to 16 bytes is one load and one store (store_partial: at most four), a longer
+// one 16-byte blocks, the last of them ending at the header's end (it overlaps the block before it with the same bytes)
+__device__ __forceinline__ void quic_put_header(uint8_t *dst, const uint8_t *src, u32 A, u32 fmask, u32 pn_len, u32 m14)
+{
+    if (A <= 16) {
+        u32x4 v = A == 16 ? u32x4(*(const u32x4_u *)src) : load_partial(src, A);
+        v[0] ^= fmask;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k)
+            if (k < pn_len)
+                v = quic_xor_byte(v, A - pn_len + k, m14 >> (8 * k));
+        if (A == 16)
+            *(u32x4_u *)dst = v;
+        else
+            store_partial(dst, v, A);
+        return;
+    }
+    u32x4 v0 = *(const u32x4_u *)src, last = *(const u32x4_u *)(src + A - 16);  // (both read before anything is written)
+    v0[0] ^= fmask;
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k)
+        if (k < pn_len)
+            last = quic_xor_byte(last, 16 - pn_len + k, m14 >> (8 * k));
+    *(u32x4_u *)dst = v0;
+    if (dst != src)
+        for (u32 o = 16; o + 16 < A; o += 16)
+            *(u32x4_u *)(dst + o) = *(const u32x4_u *)(src + o);
+    *(u32x4_u *)(dst + A - 16) = last;
+}
+
+// The open's pre-pass (RFC 9001 §5.4.2, RFC 9000 A.3): the mask from the sample 4 bytes behind the packet-number
+// offset, the first byte and the packet number unmasked, the full packet number from the expected one (r.seq), the
+// rejections and the key-phase verdict into results[i] (status OK until quic_status_kernel has the tag check), the
+// unprotected header to out + out_off and the batch kernel's descriptor to desc[i]. In place the header bytes written
+// are the header bytes read; the ciphertext behind them is not touched.
+template <int NR>
+__global__ __launch_bounds__(QUIC_AUX_WG) void quic_unmask_kernel(const KeyEntry *hp_keys, u32 hp_nkeys, u32 nkeys,
+                                                          const ptls_mi355x_record_t *recs, u64 n, const uint8_t *in, uint8_t *out,
+                                                          ptls_mi355x_quic_result_t *results, ptls_mi355x_record_t *desc)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    lds_u8 *lds = (lds_u8 *)smem;
+    check_lds_base(smem);
+    build_aes_tables(lds);
+    __syncthreads();
+    const u32 laneoff = (threadIdx.x & 31) * 4;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const ptls_mi355x_record_t r = recs[i];
+        u32x4 res = {0, 0, 0, (u32)PTLS_MI355X_QUIC_REJECTED << 16};
+        bool pass = false;
+        u32 A = 0, T = 0;
+        u64 pnum = 0;
+        // len: the packet number, the ciphertext and the tag; 4 + 16 of them are the sample's bytes at the least
+        if (r.len >= 20 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.aad_len >= 1 && r.key_idx < nkeys && r.key_idx < hp_nkeys) {
+            const uint8_t *p = in + r.in_off, *pn = p + r.aad_len;
+            const u32x4 x = quic_mask<NR>(lds, laneoff, hp_keys + r.key_idx, *(const u32x4_u *)(pn + 4));
+            u32 first = p[0];
+            first ^= x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu);
+            const u32 pn_len = (first & 3) + 1, m14 = x[0] >> 8 | x[1] << 24;  // mask[1 .. 4]
+            u32 trunc = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; ++k) {
+                if (k < pn_len)
+                    trunc = trunc << 8 | (((u32)pn[k] ^ (m14 >> (8 * k))) & 0xff);
+            }
+            // RFC 9000 A.3: the candidate in the expected number's window, moved a window up or down when that is closer
+            const u64 win = 1ull << (8 * pn_len), hwin = win >> 1;
+            u64 cand = (r.seq & ~(win - 1)) | trunc;
+            if (cand + hwin <= r.seq && cand < (1ull << 62) - win)
+                cand += win;
+            else if (cand > r.seq + hwin && cand >= win)
+                cand -= win;
+            const bool phase = (first & 0x80) == 0 && ((first >> 2) & 1) != (r.flags & 1u);
+            A = (u32)r.aad_len + pn_len, T = r.len - pn_len - 16, pnum = cand, pass = !phase;
+            res.x = (u32)cand, res.y = (u32)(cand >> 32), res.z = T;
+            res.w = pn_len | first << 8 | (u32)(phase ? PTLS_MI355X_QUIC_KEY_PHASE : PTLS_MI355X_QUIC_OK) << 16;
+            if (pass)
+                quic_put_header(out + r.out_off, p, A, first ^ p[0], pn_len, m14);
+        }
+        *(u32x4_u *)(results + i) = res;
+        quic_put_desc(desc + i, r, pass, A, T, pnum);
+    }
+}
+
+// The seal's pre-pass: the rejections (aad_len < 1 + pn_len, pn_len + len < 4: no full sample, flags != 0, a key_idx
+// not below both keysets' sizes, len above the limit) and the batch kernel's descriptor
+__global__ __launch_bounds__(256) void quic_seal_check_kernel(u32 hp_nkeys, u32 nkeys, const ptls_mi355x_record_t *recs, u64 n,
+                                                              const uint8_t *in, ptls_mi355x_record_t *desc)
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const ptls_mi355x_record_t r = recs[i];
+        bool pass = r.aad_len >= 2 && r.flags == 0 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.key_idx < nkeys && r.key_idx < hp_nkeys;
+        if (pass) {
+            const u32 pn_len = ((u32)in[r.in_off] & 3) + 1;
+            pass = r.aad_len >= 1 + pn_len && pn_len + r.len >= 4;
+        }
+        quic_put_desc(desc + i, r, pass, r.aad_len, r.len, r.seq);
+    }
+}
+
+// The seal's finish (RFC 9001 §5.4.1), after the batch kernel has written ciphertext and tag: the mask of the sample at
+// packet offset A - pn_len + 4 of the output (it may reach into the tag), and the protected header to out + out_off
+template <int NR>
+__global__ __launch_bounds__(QUIC_AUX_WG) void quic_protect_kernel(const KeyEntry *hp_keys, const ptls_mi355x_record_t *desc, u64 n,
+                                                           const uint8_t *in, uint8_t *out)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    lds_u8 *lds = (lds_u8 *)smem;
+    check_lds_base(smem);
+    build_aes_tables(lds);
+    __syncthreads();
+    const u32 laneoff = (threadIdx.x & 31) * 4;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        const ptls_mi355x_record_t d = desc[i];
+        if (d.len == QUIC_DESC_REFUSED)
+            continue;
+        const uint8_t *p = in + d.in_off;
+        uint8_t *o = out + d.out_off;
+        const u32 A = d.aad_len, first = p[0], pn_len = (first & 3) + 1;
+        const u32x4 x = quic_mask<NR>(lds, laneoff, hp_keys + d.key_idx, *(const u32x4_u *)(o + A - pn_len + 4));
+        quic_put_header(o, p, A, x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu), pn_len, x[0] >> 8 | x[1] << 24);
+    }
+}
+
+// The open's finish: the batch kernel's tag check into the status the pre-pass left OK (ok[i] is at the packet's batch
+// index whichever order the kernel walked; it is 0 already for a packet the pre-pass did not pass: record_ok refused it)
+__global__ __launch_bounds__(256) void quic_status_kernel(uint8_t *ok, ptls_mi355x_quic_result_t *results, u64 n)
+{
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
+        if (ok[i] != 0)  // (the common case reads the ok bytes alone)
+            continue;
+        uint8_t *st = (uint8_t *)(results + i) + offsetof(ptls_mi355x_quic_result_t, status);
+        if (*st == PTLS_MI355X_QUIC_OK)
+            *st = PTLS_MI355X_QUIC_BAD_MAC;
+    }
+}
+
 // QUIC-LB connection-ID cipher (lib/quiclb-impl.h:100-162, behind ptls_fusion_quiclb lib/fusion.c:2186-2233): a 4-round
 // Feistel network over the two halves of a 7..19-byte CID, each round X ^ AES-ECB((Y & mask) | len_pass) with
 // len_pass = {0 x 14, len, round} (:134-135, :47-70). One thread per CID; blocks are LE words (byte i of the block in

@@ -1395,11 +1395,13 @@ __global__ __launch_bounds__(ENGINE_WG) __attribute__((amdgpu_waves_per_eu(ENGIN
                     if (j != G - 1) {
                     } else if (OPEN) {
                         const u32x4 rt = *(const u32x4_u *)(args.in + r.in_off + frame_in_skip<OPEN, FRAME>() +
+                                                            quic_skip<FRAME>(gcm_aad_len<OPEN, FRAME>(r)) +
                                                             gcm_text_len<OPEN, FRAME>(r));
                         const u32x4 d = rt ^ tag;
                         args.ok[ok_at(pos + lo)] = (d[0] | d[1] | d[2] | d[3]) == 0;
                     } else {
-                        *(u32x4_u *)(args.out + r.out_off + frame_out_skip<OPEN, FRAME>() + gcm_text_len<OPEN, FRAME>(r)) = tag;
+                        *(u32x4_u *)(args.out + r.out_off + frame_out_skip<OPEN, FRAME>() +
+                                     quic_skip<FRAME>(gcm_aad_len<OPEN, FRAME>(r)) + gcm_text_len<OPEN, FRAME>(r)) = tag;
                     }
                 }
             }

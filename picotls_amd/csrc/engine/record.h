@@ -163,7 +163,17 @@ __device__ __forceinline__ constexpr u32 frame_in_skip()
 template <bool OPEN, int FRAME>
 __device__ __forceinline__ constexpr u32 frame_out_skip()
 {
-    return FRAME && !OPEN ? TLS_HEADER_SIZE + (FRAME == 2 ? TLS12_RECORD_IV_SIZE : 0) : 0;
+    return (FRAME == 1 || FRAME == 2) && !OPEN ? TLS_HEADER_SIZE + (FRAME == 2 ? TLS12_RECORD_IV_SIZE : 0) : 0;
+}
+// QUIC packets (FRAME = 3; RFC 9001 §5.3): the AAD is the packet's header, A = aad_len | flags << 16 bytes at the
+// packet's start, and the GCM text follows it on both arenas (frame_in_skip and frame_out_skip are 0; quic_skip adds A).
+// A seal takes the header from in + in_off; an open takes the unprotected header that quic_unmask_kernel, launched
+// ahead of it, left at out + out_off. The descriptors are the pre-passes' rewritten ones (aux_kernels.h), never the
+// caller's: offsets are the 64-bit in_off / out_off throughout, aad_off is not read.
+template <int FRAME>
+__device__ __forceinline__ constexpr u32 quic_skip(u32 A)
+{
+    return FRAME == 3 ? A : 0u;
 }
 // G-lane steps of a record's GHASH stream [pad | AAD | text | length]
 template <bool OPEN, int FRAME>

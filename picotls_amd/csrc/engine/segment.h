@@ -71,8 +71,8 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     const u32 Lsrc = SEAL_FRAME ? L - 1 : L;
     const u32 na = (A + 15) >> 4, nb = (L + 15) >> 4;
     const u32 total = na + nb + 1;
-    const uint8_t *src = args.in + r.in_off + frame_in_skip<OPEN, FRAME>();
-    uint8_t *dst = args.out + r.out_off + frame_out_skip<OPEN, FRAME>();
+    const uint8_t *src = args.in + r.in_off + frame_in_skip<OPEN, FRAME>() + quic_skip<FRAME>(A);
+    uint8_t *dst = args.out + r.out_off + frame_out_skip<OPEN, FRAME>() + quic_skip<FRAME>(A);
     int P;
     u32 N;
     if (aligned) {  // text block b at position P + na + b, and (dst / 16 + b) mod G == that position mod G
@@ -117,7 +117,11 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     const u32 n0 = iv0 ^ rk[0][0];
     const u32 n1 = iv1 ^ nw1 ^ rk[0][1];
     const u32 n2 = iv2 ^ nw2 ^ rk[0][2];
-    const uint8_t *aadp = OPEN_FRAME ? args.in + r.in_off : args.aad + r.aad_off;
+    // (a QUIC packet's AAD is its header in the clear: the seal's input, or what the open's pre-pass left in the output)
+    constexpr bool QUIC = FRAME == 3;
+    const uint8_t *aadp = QUIC         ? (OPEN ? (const uint8_t *)args.out + r.out_off : args.in + r.in_off)
+                          : OPEN_FRAME ? args.in + r.in_off
+                                       : args.aad + r.aad_off;
 
     acc = u32x4{0, 0, 0, 0};
 

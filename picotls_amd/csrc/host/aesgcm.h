@@ -1,5 +1,5 @@
 // picotls_amd/csrc/host/aesgcm.h -- host side of the AES-GCM engine: the keyset, the launches, the batch C ABI of
-// include/picotls/mi355x.h, the per-record path and the debug hooks of include/picotls/mi355x_debug.h.
+// include/picotls/mi355x.h and include/picotls/mi355x_quic.h, the per-record path and the debug hooks of include/picotls/mi355x_debug.h.
 // Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip (included after host/runtime.h; not standalone).
 #ifndef PTLS_MI355X_HOST_AESGCM_H
 #define PTLS_MI355X_HOST_AESGCM_H
@@ -11,11 +11,16 @@ static std::atomic<uint64_t> g_launches[8];
 
 // The instantiations of gcm_chunked_kernel<NR, OPEN, FRAME, true, EXT> (the CT argument is instantiated true only,
 // launch_chunked_x), for NR 10 and 14: EXT 1 (a spread plan) serves unframed batches, EXT 2 (header-protection masks)
-// unframed seals, EXT 0, 3, 4 and 5 every frame and direction. set_kernel_attrs enumerates the set through this
-// predicate and launch_chunked_x asserts it, so whatever is launched has its dynamic LDS size set.
+// unframed seals, EXT 0, 3, 4 and 5 every frame and direction -- but EXT 3 not QUIC packets (frame 3), whose long whole
+// runs the serial kernel takes (launch_chunked). set_kernel_attrs enumerates the set through this predicate and
+// launch_chunked_x asserts it, so whatever is launched has its dynamic LDS size set.
 constexpr bool chunked_instance(int frame, bool open, int ext)
 {
-    return frame < 0 || frame > 2 || ext < 0 || ext > 5 ? false : ext == 1 ? frame == 0 : ext == 2 ? frame == 0 && !open : true;
+    return frame < 0 || frame > 3 || ext < 0 || ext > 5 ? false
+           : ext == 1                                   ? frame == 0
+           : ext == 2                                   ? frame == 0 && !open
+           : ext == 3                                   ? frame != 3
+                                                        : true;
 }
 
 // (deduced return types and a left fold: such a template is instantiated where it is named and a left fold from its
@@ -41,7 +46,7 @@ static auto chunked_attrs_at(std::index_sequence<I...>)
 }
 
 template <int... EXT>
-static auto chunked_attrs() { return chunked_attrs_at<EXT...>(std::make_index_sequence<3 * sizeof...(EXT) * 4>{}); }
+static auto chunked_attrs() { return chunked_attrs_at<EXT...>(std::make_index_sequence<4 * sizeof...(EXT) * 4>{}); }
 
 static int set_kernel_attrs(void)
 {
@@ -55,6 +60,8 @@ static int set_kernel_attrs(void)
                         gcm_batch_kernel<14, true>) == 0 &&
                     chunked_attrs<1>() == 0 && chunked_attrs<2>() == 0 && chunked_attrs<3, 4, 5>() == 0 && chunked_attrs<0>() == 0 &&
                     lds(LDS_AES_BYTES, ecb_kernel<10>, ecb_kernel<14>, hp_kernel<10>, hp_kernel<14>, quiclb_kernel<10>) == 0 &&
+                    lds(LDS_AES_BYTES, quic_unmask_kernel<10>, quic_unmask_kernel<14>, quic_protect_kernel<10>,
+                        quic_protect_kernel<14>) == 0 &&
                     lds(SPAN_LDS, gcm_span_kernel<10, false, true>, gcm_span_kernel<10, true, true>, gcm_span_kernel<14, false, true>,
                         gcm_span_kernel<14, true, true>) == 0;
     return ok ? 0 : -1;
@@ -97,6 +104,13 @@ struct st_ptls_mi355x_keyset_t {
     // one buffer per stream (allocated on the stream's first pair; a stream orders its own pairs), so that pairs on
     // several streams run concurrently; at most W8_FLAG_STREAMS (StreamSlots)
     StreamSlots<u32 *, W8_FLAG_STREAMS> w8flags;
+    // QUIC packets (launch_quic): the descriptors the pre-pass writes for the batch kernel, grown on demand in stream
+    // order; quic_stream: the stream of the last call that used them (a call on another stream waits for that one's
+    // use event, as for the spread scratch)
+    ptls_mi355x_record_t *d_quic;
+    size_t quic_cap;  // its descriptors
+    hipStream_t quic_stream;
+    bool quic_used;
 };
 
 static int mark_ready(ptls_mi355x_keyset_t *ks, hipStream_t s);
@@ -333,6 +347,8 @@ void ptls_mi355x_keyset_free(ptls_mi355x_keyset_t *ks)
         (void)hipFreeAsync(ks->d_group, ds->maint);
     if (ks->d_spread != nullptr)
         (void)hipFreeAsync(ks->d_spread, ds->maint);
+    if (ks->d_quic != nullptr)
+        (void)hipFreeAsync(ks->d_quic, ds->maint);
     for (auto &f : ks->w8flags.v)
         (void)hipFreeAsync(f.second, ds->maint);
     ks->w8flags.v.clear();
@@ -576,7 +592,8 @@ static void launch_chunked(unsigned grid, hipStream_t s, const BatchArgs &a)
     // nor a batch of fewer than W8_MIN_RECS records (the table build is not repaid). TLS 1.2 framing too (faster despite
     // EXT 4's 96-byte-per-lane seal spill, common.h).
     if (!a.one_inline && a.done_flag == nullptr && a.nrecs >= W8_MIN_RECS) {
-        const bool whole_possible = a.chunk != 0 || a.bounds != nullptr || (a.nrecs + grid - 1) / grid >= WHOLE_MIN_RECS;
+        // (QUIC packets, FRAME 3: the serial kernel alone, for whole runs of long packets too; EXT 3 is not instantiated for them)
+        const bool whole_possible = FRAME != 3 && (a.chunk != 0 || a.bounds != nullptr || (a.nrecs + grid - 1) / grid >= WHOLE_MIN_RECS);
         BatchArgs b = a;
         b.w8_split = whole_possible ? 2u : 1u;
         if (!whole_possible)
@@ -587,8 +604,10 @@ static void launch_chunked(unsigned grid, hipStream_t s, const BatchArgs &a)
             launch_chunked_x<NR, OPEN, FRAME, 5>(grid, s, b);
         else
             launch_chunked_x<NR, OPEN, FRAME, 4>(grid, s, b);
-        if (whole_possible)
-            launch_chunked_x<NR, OPEN, FRAME, 3>(grid, s, b);
+        if constexpr (FRAME != 3) {
+            if (whole_possible)
+                launch_chunked_x<NR, OPEN, FRAME, 3>(grid, s, b);
+        }
         return;
     }
     launch_chunked_x<NR, OPEN, FRAME>(grid, s, a);
@@ -681,6 +700,8 @@ static int launch_gcm(const GcmLaunch &g)
             launch_chunked<NR, OPEN, 1>((unsigned)grid, s, a);
         else if (g.frame == 2)
             launch_chunked<NR, OPEN, 2>((unsigned)grid, s, a);
+        else if (g.frame == 3)
+            launch_chunked<NR, OPEN, 3>((unsigned)grid, s, a);
         else if (chunked)
             launch_chunked<NR, OPEN, 0>((unsigned)grid, s, a);
         else {
@@ -793,7 +814,8 @@ static uint8_t *spread_scratch_locked(ptls_mi355x_keyset_t *ks, hipStream_t s, s
 // A batch call on a keyset: waits for the keyset's setup, groups an ungrouped many-key batch by key on the device, launches,
 // and records the use (teardown and rekey are ordered after it).
 static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_record_t *recs, size_t nrecs, const void *in,
-                        const void *aad, void *out, uint8_t *ok, void *stream, int frame = 0, const HpLaunch *hpl = nullptr)
+                        const void *aad, void *out, uint8_t *ok, void *stream, int frame = 0, const HpLaunch *hpl = nullptr,
+                        std::unique_lock<std::mutex> *held = nullptr)
 {
     if (ks == NULL || (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && ok == NULL))))
         return fail("%s", "batch: invalid arguments");
@@ -809,17 +831,21 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
                        nrecs <= 0xffffffffu;
     // the keyset's scratch (spread pieces, key grouping) is shared by its launches on every stream: ks->mu is held from
     // taking it through the launch and the use event after it
-    std::unique_lock<std::mutex> lk(ks->mu, std::defer_lock);
+    // (launch_quic holds it already, around its own launches before and after this one: `held`, which stays locked)
+    std::unique_lock<std::mutex> own(ks->mu, std::defer_lock);
+    std::unique_lock<std::mutex> &lk = held != nullptr ? *held : own;
     GcmLaunch g = {};
     g.a.keys = ks->d_keys, g.a.nkeys = (u32)ks->nkeys, g.a.recs = recs, g.a.nrecs = nrecs, g.a.unit_log2 = CHUNK_LOG2;
     g.a.in = (const uint8_t *)in, g.a.aad = (const uint8_t *)aad, g.a.out = (uint8_t *)out, g.a.ok = ok;
     g.stream = s, g.nr = ks->nr, g.ncu = ks->ds->ncu, g.schedule = ks->schedule, g.ct = ks->ct, g.open = open, g.frame = frame, g.hp = hpl;
     // small batches with long records: the spread scratch
     if (hpl == nullptr && spread_eligible(ks, nrecs, frame)) {
-        lk.lock();
+        if (!lk.owns_lock())
+            lk.lock();
         g.spread = spread_scratch_locked(ks, s, nrecs);
     } else if (hpl == nullptr && w8_eligible(ks, nrecs)) {  // (a spread launch never takes the W8 pair)
-        lk.lock();
+        if (!lk.owns_lock())
+            lk.lock();
         g.a.w8_flags = w8_flags_locked(ks, s);
     }
     if (group) {
@@ -894,7 +920,94 @@ static int launch_hp(const KeyEntry *keys, u32 nkeys, int nr, int ncu, const ptl
     return 0;
 }
 
+// QUIC packets (ptls_mi355x_seal_quic_packets / ptls_mi355x_open_quic_packets): the pre-pass, the FRAME 3 batch on the
+// descriptors it wrote, the finish kernel (aux_kernels.h), all on `stream` with no host work between them. The
+// descriptors live in ks's scratch (d_quic), so ks->mu is held from taking it through the last launch and the use event
+// after it. The launches read both keysets, so the call is a use of both: a free or rekey of either orders itself
+// behind it. Two distinct keysets' mutexes are taken in the order of their addresses, whichever role each has here.
+static int launch_quic(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, bool open, const ptls_mi355x_record_t *recs,
+                       size_t nrecs, const void *in, void *out, uint8_t *ok, ptls_mi355x_quic_result_t *results, void *stream)
+{
+    if (ks == NULL || hp_ks == NULL ||
+        (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && (ok == NULL || results == NULL)))))
+        return fail("%s", "quic packets: invalid arguments");
+    if (hp_ks->device != ks->device)
+        return fail("%s", "quic packets: hp_ks is on another device than ks");
+    if (nrecs == 0)
+        return 0;
+    DeviceScope scope(ks->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (wait_ready(ks, s) != 0 || (hp_ks != ks && wait_ready(hp_ks, s) != 0))
+        return -1;
+    const bool ks_first = hp_ks == ks || std::less<ptls_mi355x_keyset_t *>()(ks, hp_ks);
+    std::unique_lock<std::mutex> lk(ks->mu, std::defer_lock), lkh;
+    if (hp_ks != ks)
+        lkh = std::unique_lock<std::mutex>(hp_ks->mu, std::defer_lock);
+    if (ks_first)
+        lk.lock();
+    if (hp_ks != ks)
+        lkh.lock();
+    if (!ks_first)
+        lk.lock();
+    // the descriptor scratch: after its last user on another stream, grown in stream order on this one
+    if (ks->quic_used && ks->quic_stream != s) {
+        const hipEvent_t last = ks->uses.event_of(ks->quic_stream);
+        if (last != nullptr)
+            HIP_TRY(hipStreamWaitEvent(s, last, 0));
+    }
+    if (ks->quic_cap < nrecs) {
+        if (ks->d_quic != nullptr)
+            HIP_TRY(hipFreeAsync(ks->d_quic, s));
+        ks->d_quic = nullptr, ks->quic_cap = 0;
+        HIP_TRY(hipMallocAsync((void **)&ks->d_quic, nrecs * sizeof(ptls_mi355x_record_t), s));
+        ks->quic_cap = nrecs;
+    }
+    ks->quic_stream = s, ks->quic_used = true;
+    ptls_mi355x_record_t *desc = ks->d_quic;
+    const unsigned grid = aux_grid(nrecs, ks->ds->ncu);
+    // (the kernels with the AES tables in LDS: two workgroups of QUIC_AUX_WG threads a CU)
+    const unsigned lgrid = (unsigned)min((u64)(nrecs + QUIC_AUX_WG - 1) / QUIC_AUX_WG, (u64)ks->ds->ncu * 2);
+    const auto launch = [&] {
+        return launch_and_note(ks->uses, ks->ds, s, [&] {
+            LAUNCH_CLEAR();
+            if (open)
+                with_nr(hp_ks->nr, [&](auto NR) {
+                    quic_unmask_kernel<NR><<<lgrid, QUIC_AUX_WG, LDS_AES_BYTES, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, (u32)ks->nkeys, recs, nrecs,
+                                                                           (const uint8_t *)in, (uint8_t *)out, results, desc);
+                });
+            else
+                quic_seal_check_kernel<<<grid, 256, 0, s>>>((u32)hp_ks->nkeys, (u32)ks->nkeys, recs, nrecs, (const uint8_t *)in, desc);
+            HIP_TRY(hipGetLastError());
+            if (launch_batch(ks, open, desc, nrecs, in, NULL, out, ok, stream, 3, nullptr, &lk) != 0)
+                return -1;
+            LAUNCH_CLEAR();
+            if (open)
+                quic_status_kernel<<<grid, 256, 0, s>>>(ok, results, nrecs);
+            else
+                with_nr(hp_ks->nr, [&](auto NR) {
+                    quic_protect_kernel<NR><<<lgrid, QUIC_AUX_WG, LDS_AES_BYTES, s>>>(hp_ks->d_keys, desc, nrecs, (const uint8_t *)in, (uint8_t *)out);
+                });
+            HIP_TRY(hipGetLastError());
+            return 0;
+        });
+    };
+    return hp_ks != ks ? launch_and_note(hp_ks->uses, hp_ks->ds, s, launch) : launch();
+}
+
 extern "C" {
+
+int ptls_mi355x_seal_quic_packets(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, const ptls_mi355x_record_t *recs,
+                                  size_t nrecs, const void *in, void *out, void *stream)
+{
+    return launch_quic(ks, hp_ks, false, recs, nrecs, in, out, NULL, NULL, stream);
+}
+
+int ptls_mi355x_open_quic_packets(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, const ptls_mi355x_record_t *recs,
+                                  size_t nrecs, const void *in, void *out, uint8_t *ok, ptls_mi355x_quic_result_t *results,
+                                  void *stream)
+{
+    return launch_quic(ks, hp_ks, true, recs, nrecs, in, out, ok, results, stream);
+}
 
 int ptls_mi355x_seal_batch(ptls_mi355x_keyset_t *ks, const ptls_mi355x_record_t *recs, size_t nrecs, const void *in,
                            const void *aad, void *out, void *stream)

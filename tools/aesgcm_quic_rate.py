@@ -1,0 +1,214 @@
+#!/usr/bin/env python3
+"""QUIC packet protection in one AES-GCM call against the launches it replaces, device-resident.
+
+    python tools/aesgcm_quic_rate.py [--steps 20 --warmup 3 --rounds 5] [--shapes quic1200,quic2perkey] [--scale 1.0]
+
+Timed the way tools/chacha_quic_rate.py times: inputs already in HBM, the arms interleaved in one process (`rounds`
+times each arm in turn runs steps / rounds timed steps), the shader clock inside the batch kernels (workgroup 0 of every
+launch, ptls_mi355x_debug_kernel_clock) beside each rate. Seal and open are timed apart; a rate is payload bytes over
+wall time, GiB/s. Prints one JSON line.
+
+Arms, per direction:
+  new        seal: ptls_mi355x_seal_quic_packets (the descriptor pre-pass, the batch, the header-protection finish)
+             open: ptls_mi355x_open_quic_packets (the unmasking pre-pass, the batch, the status finish)
+  old        seal: ptls_mi355x_seal_batch_hp on an AAD arena prepared before timing; the masks are left unapplied
+             open: hp_mask_batch, then open_batch on descriptors and unmasked headers that were prepared on the host
+                   before timing, so the host round trip a real receiver makes between the two is left out
+  old_again  the old arm once more: the spread of two runs of the same code (A/A)
+Both omissions favour the old arm.
+
+Shapes: 1,048,576 x 1200 B under one AES-128 key; 131,072 x 1200 B over 65,536 keys (2 a key, distinct
+header-protection keys). Packets have a short header: first byte, an 8-byte DCID, a packet number of 1..4 bytes.
+
+Aim: new >= old x (1 - spread) for seal and for open on either shape, spread = |old - old_again| / old ("bar_met").
+Measured: profiles/aesgcm_quic.md.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from chacha_rate import in_kernel_mhz  # noqa: E402
+
+SHAPES = {
+    "quic1200": (1048576, 1200, 1),
+    "quic2perkey": (131072, 1200, 65536),
+}
+DCID = 8
+ARMS = ("new", "old", "old_again")
+
+
+def run_shape(name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int, rounds: int) -> dict:
+    import torch
+
+    import picotls_amd as pa
+    from picotls_amd.records import HP_DTYPE, QUIC_RESULT_DTYPE, RECORD_DTYPE
+
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(9001)
+    key_idx = (np.arange(n, dtype=np.uint32) * nkeys // n).astype(np.uint32)  # grouped by connection, as they arrive
+    pn_len = (np.arange(n) % 4 + 1).astype(np.int64)
+    hlen = 1 + DCID + pn_len
+    pns = rng.integers(0, 2**62, n, dtype=np.uint64)
+    slot = (1 + DCID + 4 + plen + 16 + 15) // 16 * 16
+    off = np.arange(n, dtype=np.uint64) * np.uint64(slot)
+    ks = pa.Keyset(rng.bytes(16 * nkeys), rng.bytes(12 * nkeys), 16)
+    hp_ks = pa.Keyset(rng.bytes(16 * nkeys), bytes(12 * nkeys), 16)
+
+    # the cleartext packets, built on the device: header || payload in slots of `slot` bytes
+    clear = torch.randint(0, 256, (n, slot), dtype=torch.uint8, device=dev)
+    t_pnl = torch.from_numpy(pn_len).to(dev)
+    t_pn = torch.from_numpy(pns.astype(np.int64)).to(dev)
+    clear[:, 0] = (0x40 | (t_pnl - 1)).to(torch.uint8)
+    for ln in (1, 2, 3, 4):
+        rows = torch.nonzero(t_pnl == ln).reshape(-1)
+        for i in range(ln):
+            clear[rows, 1 + DCID + i] = ((t_pn[rows] >> (8 * (ln - 1 - i))) & 0xff).to(torch.uint8)
+    clear = clear.reshape(-1)
+
+    def recs(**cols):
+        r = np.zeros(n, RECORD_DTYPE)
+        r["key_idx"] = key_idx
+        for k, v in cols.items():
+            r[k] = v
+        return torch.from_numpy(r.view(np.uint8).copy()).to(dev)
+
+    # new: whole packets; old: the payload with the cleartext header as the AAD (seal reads it from the cleartext arena,
+    # open from the same arena: the unmasked headers a receiver would have rebuilt on the host)
+    d_seal_new = recs(in_off=off, out_off=off, seq=pns, len=plen, aad_len=hlen)
+    d_open_new = recs(in_off=off, out_off=off, seq=pns, len=pn_len + plen + 16, aad_len=hlen - pn_len)
+    d_old = recs(in_off=off + hlen.astype(np.uint64), out_off=off + hlen.astype(np.uint64), seq=pns, len=plen, aad_off=off, aad_len=hlen)
+    hp = np.zeros(n, HP_DTYPE)
+    hp["sample_off"], hp["key_idx"] = off + (hlen - pn_len + 4).astype(np.uint64), key_idx
+    d_hp = torch.from_numpy(hp.view(np.uint8).copy()).to(dev)
+    d_wire = torch.zeros(n * slot, dtype=torch.uint8, device=dev)      # protected packets (new seal), the opens' input
+    d_sealed = torch.zeros(n * slot, dtype=torch.uint8, device=dev)    # the old seal's output
+    d_back = torch.zeros(n * slot, dtype=torch.uint8, device=dev)
+    d_masks = torch.zeros(16 * n, dtype=torch.uint8, device=dev)
+    d_ok = torch.zeros(n, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(16 * n, dtype=torch.uint8, device=dev)
+    sp = torch.cuda.current_stream(dev).cuda_stream
+
+    def seal_new():
+        pa.seal_quic_packets(ks, hp_ks, d_seal_new.data_ptr(), n, clear.data_ptr(), d_wire.data_ptr(), sp)
+
+    def seal_old():
+        pa.seal_batch_hp(ks, d_old.data_ptr(), n, clear.data_ptr(), clear.data_ptr(), d_sealed.data_ptr(), hp_ks, d_hp.data_ptr(),
+                         d_masks.data_ptr(), sp)
+
+    def open_new():
+        pa.open_quic_packets(ks, hp_ks, d_open_new.data_ptr(), n, d_wire.data_ptr(), d_back.data_ptr(), d_ok.data_ptr(),
+                                    d_res.data_ptr(), sp)
+
+    def open_old():
+        pa.hp_mask_batch(hp_ks, d_hp.data_ptr(), n, d_wire.data_ptr(), d_masks.data_ptr(), sp)
+        pa.open_batch(ks, d_old.data_ptr(), n, d_wire.data_ptr(), clear.data_ptr(), d_back.data_ptr(), d_ok.data_ptr(), sp)
+
+    calls = {"seal": {"new": seal_new, "old": seal_old, "old_again": seal_old},
+             "open": {"new": open_new, "old": open_old, "old_again": open_old}}
+
+    # warm up and check: the new seal's ciphertext || tag equals the old seal's, its protected header is the cleartext
+    # one under the old arm's masks, and both opens restore the packets
+    out = {"shape": name, "packets": n, "payload_len": plen, "keys": nkeys, "payload_bytes": n * plen}
+    for _ in range(max(warmup, 1)):
+        seal_new(), seal_old()
+    torch.cuda.synchronize(dev)
+    m = min(n, 4096)
+    cols = torch.arange(slot, device=dev)[None, :]
+    w, s, c = (t[:m * slot].reshape(m, slot) for t in (d_wire, d_sealed, clear))
+    hl = torch.from_numpy(hlen[:m]).to(dev)[:, None]
+    body = (cols >= hl) & (cols < hl + plen + 16)
+    masks = d_masks[:16 * m].reshape(m, 16)
+    hdr = c.clone()
+    hdr[:, 0] ^= masks[:, 0] & 0x1f
+    for i in range(4):
+        at = (hl[:, 0] - t_pnl[:m] + i).clamp(max=slot - 1)
+        hit = i < t_pnl[:m]
+        hdr[torch.arange(m, device=dev)[hit], at[hit]] ^= masks[hit, 1 + i]
+    seal_same = bool(torch.equal(w[body], s[body])) and bool(torch.equal(w[cols < hl], hdr[cols < hl]))
+    verified = {"seal_new_equals_old_path": seal_same}
+    want = (cols < hl + plen)
+    for arm, fn in (("new", open_new), ("old", open_old)):
+        d_back.zero_(), d_ok.zero_()
+        for _ in range(max(warmup, 1)):
+            fn()
+        torch.cuda.synchronize(dev)
+        b = d_back[:m * slot].reshape(m, slot)
+        sel = want if arm == "new" else (cols >= hl) & want
+        verified["open_" + arm] = bool(d_ok.min().item() == 1) and bool(torch.equal(b[sel], c[sel]))
+    res = d_res.cpu().numpy().view(QUIC_RESULT_DTYPE)
+    verified["results"] = bool(np.array_equal(res["pn"], pns) and (res["status"] == 0).all() and np.array_equal(res["pn_len"], pn_len))
+    out["verified"] = verified
+
+    per_round = max(steps // rounds, 1)
+    kcap = 4 * per_round + 8
+    kclk = torch.zeros(4 * kcap, dtype=torch.int64, device=dev)
+    for direction in ("seal", "open"):
+        wall = {a: 0.0 for a in ARMS}
+        clocks = {a: [] for a in ARMS}
+        for _ in range(rounds):
+            for arm in ARMS:
+                pa.debug_kernel_clock(kclk.data_ptr(), kcap)
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                for _ in range(per_round):
+                    calls[direction][arm]()
+                torch.cuda.synchronize(dev)
+                wall[arm] += time.perf_counter() - t0
+                nk = min(pa.debug_kernel_clock_count(), kcap)
+                clocks[arm].append(kclk[:4 * nk].cpu().numpy().copy())
+        pa.debug_kernel_clock(0, 0)
+        d = {}
+        for arm in ARMS:
+            k = per_round * rounds
+            d[arm] = {"steps": k, "ms_per_step": round(wall[arm] / k * 1e3, 4),
+                      "gib_per_s": round(n * plen * k / wall[arm] / 2**30, 1),
+                      "in_kernel_mhz": in_kernel_mhz(pa, np.concatenate(clocks[arm]))}
+        d["aa_spread"] = round(abs(d["old"]["gib_per_s"] - d["old_again"]["gib_per_s"]) / d["old"]["gib_per_s"], 4)
+        d["new_over_old"] = round(d["new"]["gib_per_s"] / d["old"]["gib_per_s"], 3)
+        d["bar_met"] = d["new"]["gib_per_s"] >= d["old"]["gib_per_s"] * (1 - d["aa_spread"])
+        out[direction] = d
+    out["counters"] = pa.debug_counters(reset=True)
+    ks.free(), hp_ks.free()
+    del clear, d_wire, d_sealed, d_back, d_masks, d_ok, d_res
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--shapes", default="quic1200,quic2perkey")
+    p.add_argument("--scale", type=float, default=1.0, help="packet counts times this (smaller runs)")
+    args = p.parse_args()
+    import torch
+
+    import picotls_amd as pa
+
+    assert torch.cuda.is_available(), "needs an MI355X"
+    pa.load_library()
+    pa.debug_counters(reset=True)
+    shapes = []
+    for name in [s for s in args.shapes.split(",") if s]:
+        n, plen, nkeys = SHAPES[name]
+        n = max(int(n * args.scale), 4)
+        shapes.append(run_shape(name, n, plen, min(nkeys, n), args.steps, args.warmup, args.rounds))
+    print(json.dumps({"tool": "aesgcm_quic_rate", "metric": "GiB/s over payload bytes, seal and open apart, device-resident",
+                      "shapes": shapes, "aim": "new >= old x (1 - A/A spread), seal and open, every shape",
+                      "bar_met": all(s[d]["bar_met"] for s in shapes for d in ("seal", "open")),
+                      "verified": all(all(s["verified"].values()) for s in shapes)}))
+
+
+if __name__ == "__main__":
+    main()
