@@ -184,6 +184,8 @@ int ptls_mi355x_ecb_batch(ptls_mi355x_keyset_t *ks, const uint32_t *key_idx, con
  * ciphertext including the inner type and padding). The plaintext (len bytes) goes to out + out_off. ok[i] = 1 only
  * if the tag verifies, the header is {23, 3, 3, BE16(len + 16)} and an inner content type is found; results (may be
  * NULL) gives the content length after stripping the type and the zero padding, the inner type and a status.
+ * A record whose header is not that one has nothing written to out, whether its tag verifies (BAD_HEADER) or not
+ * (BAD_MAC); a record with that header whose tag fails has its len bytes written, as ptls_aead_decrypt writes them.
  */
 #define PTLS_MI355X_TLS_OK 0
 #define PTLS_MI355X_TLS_BAD_MAC 1            /* PTLS_ALERT_BAD_RECORD_MAC */
@@ -213,7 +215,8 @@ int ptls_mi355x_open_tls_records(ptls_mi355x_keyset_t *ks, const ptls_mi355x_rec
  * header {type, 3, 3, BE16(len + 24)} || explicit nonce || ciphertext || tag (len + 37 bytes).
  * open_tls12_records: in + in_off is the wire record, recs[i].len = header length field - 24; the plaintext goes to
  * out + out_off. ok[i] = 1 only if the tag verifies and the header is {type, 3, 3, BE16(len + 24)}; results (may be
- * NULL) gets plain_len = len, the record's content type and a status.
+ * NULL) gets plain_len = len, the record's content type and a status. As in open_tls_records, a record with another
+ * header has nothing written to out.
  */
 int ptls_mi355x_seal_tls12_records(ptls_mi355x_keyset_t *ks, const ptls_mi355x_record_t *recs, size_t nrecs, const void *in,
                                    void *out, void *stream);

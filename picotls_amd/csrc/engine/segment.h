@@ -32,6 +32,13 @@
 // lockstep one) is read nowhere since the segment ends became one: it only keeps the lockstep kernel's instantiation
 // apart from the spread and span kernels'. Sharing one, the step lambdas below gain callers, the compiler inlines them
 // otherwise, and the four lockstep kernels' code changes (21 to 38 lines each).
+// a 16-byte store of gcm_segment's text output: unconditional but in a framed open (HDR), which skips it for a record
+// whose header is refused (wr, set at the function's start)
+#define SEG_PUT(p, v)              \
+    do {                           \
+        if (!HDR || wr)            \
+            *(u32x4_u *)(p) = (v); \
+    } while (0)
 template <int NR, bool OPEN, int FRAME = 0, bool CT = false, bool W8 = false, int GG = ENGINE_G, bool MK4 = false>
 __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 *lds, const u32 (&rk)[NR + 1][4], u32 iv0,
                                             u32 iv1, u32 iv2, const ptls_mi355x_record_t &r, bool valid, u32 m_lo,
@@ -73,6 +80,21 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     const u32 total = na + nb + 1;
     const uint8_t *src = args.in + r.in_off + frame_in_skip<OPEN, FRAME>() + quic_skip<FRAME>(A);
     uint8_t *dst = args.out + r.out_off + frame_out_skip<OPEN, FRAME>() + quic_skip<FRAME>(A);
+    // A framed open writes no plaintext for a record whose header the record layer refuses (TLS 1.3: not {23, 3, 3,
+    // BE16(len + 16)}; TLS 1.2: not {type, 3, 3, BE16(8 + len + 16)}, the checks of tls_unpad_kernel and
+    // tls12_check_kernel): its range of the output stays as it was. Its tag is computed all the same, since those
+    // kernels report a failed tag ahead of a bad header. HDR is false in every other instantiation, whose stores
+    // (SEG_PUT) are then unconditional.
+    constexpr bool HDR = OPEN && (FRAME == 1 || FRAME == 2);
+    bool wr = true;
+    if constexpr (HDR) {
+        if (valid) {
+            const uint8_t *h = args.in + r.in_off;
+            const u32 w = *(const u32_u *)h, wl = (w >> 24) << 8 | h[4];
+            wr = FRAME == 1 ? (w & 0xffffffu) == 0x030317u && wl == L + 16
+                            : (w & 0xffff00u) == 0x030300u && wl == L + TLS12_RECORD_IV_SIZE + 16;
+        }
+    }
     int P;
     u32 N;
     if (aligned) {  // text block b at position P + na + b, and (dst / 16 + b) mod G == that position mod G
@@ -181,7 +203,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
         if (__all(!act || full)) {
             const u32x4 o = cur ^ ks;
             if (act)
-                *(u32x4_u *)(dst + 16u * (u32)b) = o;
+                SEG_PUT(dst + 16u * (u32)b, o);
             return OPEN ? cur : o;
         }
         if (is_data) {
@@ -190,7 +212,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
             if (rem >= 16 && (!SEAL_FRAME || Lsrc - 16u * (u32)b >= 16)) {
                 const u32x4 v = cur;
                 const u32x4 o = v ^ ks;
-                *(u32x4_u *)op = o;
+                SEG_PUT(op, o);
                 X = OPEN ? v : o;
             } else {
                 const u32 srem = Lsrc - 16u * (u32)b;
@@ -199,8 +221,8 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
                     v[srem >> 2] |= (u32)(r.flags & 0xffu) << (8 * (srem & 3));
                 const u32x4 o = rem >= 16 ? v ^ ks : mask_tail(v ^ ks, rem);
                 if (rem >= 16)
-                    *(u32x4_u *)op = o;
-                else
+                    SEG_PUT(op, o);
+                else if (!HDR || wr)
                     store_partial(op, o, rem);
                 X = OPEN ? v : o;
             }
@@ -344,9 +366,9 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
                     if (first == late) {  // the held line is whole at this step (held from inside the range only)
                         uint8_t *p = dst_l + off;
                         if (s >= sa + 1 + (int)late)
-                            *(u32x4_u *)(p - 64) = held;
+                            SEG_PUT(p - 64, held);
                         if (!late || s > sa)
-                            *(u32x4_u *)p = held2;
+                            SEG_PUT(p, held2);
                     }
                     if (first)
                         held = o;
@@ -369,7 +391,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
                     else
                         *(u32x4_u *)(dst + off) = o;
                 } else {
-                    *(u32x4_u *)(dst + off) = o;
+                    SEG_PUT(dst + off, o);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (W8)
@@ -383,11 +405,11 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
             if constexpr (LINE) {  // the blocks still held after the range's last step
                 uint8_t *p = dst + off - 16 * G;
                 if ((((u32)(uintptr_t)p) & 64u) == 0) {
-                    *(u32x4_u *)p = held;
+                    SEG_PUT(p, held);
                 } else if (late) {
-                    *(u32x4_u *)p = held2;
+                    SEG_PUT(p, held2);
                     if (sb - 1 > sa)
-                        *(u32x4_u *)(p - 64) = held;
+                        SEG_PUT(p - 64, held);
                 }
             }
             s0 = (u32)sb;  // (a block in the range's last step is stored at once: nothing is held past it)
@@ -490,5 +512,7 @@ __device__ __forceinline__ void gcm_segment(const BatchArgs &args, const lds_u8 
     }
 #endif
 }
+
+#undef SEG_PUT
 
 #endif  // PTLS_MI355X_ENGINE_SEGMENT_H

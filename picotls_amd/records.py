@@ -2,7 +2,8 @@
 
 A batch is described by a ``RECORD_DTYPE`` array (the 40-byte ``ptls_mi355x_record_t`` of include/picotls/mi355x.h)
 plus three byte arenas: the input arena (plaintext when sealing; ciphertext||tag when opening), the output arena and
-the AAD arena. Record slots are 16-byte aligned so the kernels' 16-byte accesses stay inside one record.
+the AAD arena. ``RecordBatch.build`` aligns record slots to 16 bytes so the kernels' 16-byte accesses stay inside one
+record; the C ABI asks for no alignment, and ``RecordBatch.build_offsets`` packs records byte-adjacent from any base.
 """
 from __future__ import annotations
 
@@ -94,6 +95,41 @@ class RecordBatch:
         opn["in_off"], opn["out_off"] = sealed_off, pt_off
         return cls(seal, opn, int(pt_slot.sum()) if n else 0, int(sealed_slot.sum()) if n else 0,
                    int(aad_slot.sum()) if n else 0)
+
+    PACKED_TAIL = 64  # bytes after the last record of each arena of build_offsets
+
+    @classmethod
+    def build_offsets(cls, lens, aad_lens, seqs=None, key_idx=None, in_base=0, out_base=0, aad_base=0,
+                      in_place=False) -> "RecordBatch":
+        """Packs records byte-adjacent, without alignment or padding: record i + 1 begins on the byte after record i ends
+        in all three arenas (plaintext stride ``len``, sealed stride ``len + 16``, AAD stride ``aad_len``), the first
+        record at ``in_base`` / ``out_base`` / ``aad_base`` (any byte, odd ones included). The arena sizes include
+        ``PACKED_TAIL`` bytes after the last record.
+
+        With ``in_place`` the plaintext lies where its ciphertext goes: ``seal`` and ``open`` have ``in_off == out_off``
+        in the sealed arena (stride ``len + 16``, first record at ``out_base``), and ``pt_bytes == sealed_bytes``."""
+        lens = np.asarray(lens, dtype=np.uint64)
+        n = len(lens)
+        aad_lens = np.broadcast_to(np.asarray(aad_lens, dtype=np.uint64), (n,))
+        seqs = np.arange(n, dtype=np.uint64) if seqs is None else np.asarray(seqs, dtype=np.uint64)
+        key_idx = np.zeros(n, dtype=np.uint32) if key_idx is None else np.asarray(key_idx, dtype=np.uint32)
+
+        def packed(base, sizes):
+            ends = np.uint64(base) + np.cumsum(sizes, dtype=np.uint64)
+            return np.concatenate([[np.uint64(base)], ends[:-1]]).astype(np.uint64) if n else np.zeros(0, np.uint64), \
+                (int(ends[-1]) if n else int(base)) + cls.PACKED_TAIL
+
+        sealed_off, sealed_bytes = packed(out_base, lens + np.uint64(16))
+        pt_off, pt_bytes = (sealed_off, sealed_bytes) if in_place else packed(in_base, lens)
+        aad_off, aad_bytes = packed(aad_base, aad_lens)
+        if aad_bytes >= 1 << 32:
+            raise ValueError("AAD arena exceeds 4 GiB (aad_off is 32-bit)")
+        seal = np.zeros(n, dtype=RECORD_DTYPE)
+        seal["in_off"], seal["out_off"], seal["seq"] = pt_off, sealed_off, seqs
+        seal["aad_off"], seal["len"], seal["key_idx"], seal["aad_len"] = aad_off, lens, key_idx, aad_lens
+        opn = seal.copy()
+        opn["in_off"], opn["out_off"] = sealed_off, pt_off
+        return cls(seal, opn, pt_bytes, sealed_bytes, aad_bytes)
 
 
 def algorithmic_bytes(lens, aad_lens, is_seal: bool) -> int:

@@ -26,6 +26,50 @@ def test_empty_batch():
     assert b.n == 0 and b.pt_bytes == 0
 
 
+@pytest.mark.parametrize("in_place", [False, True])
+def test_packed_layout_is_byte_adjacent(in_place):
+    """RecordBatch.build_offsets: every record begins on the byte after its predecessor's last one in all three arenas,
+    the first at the given (odd) bases, the arenas end 64 bytes or more after the last record, and the open descriptors
+    mirror the seal ones; in place, both directions use the sealed arena's offsets."""
+    rng = np.random.default_rng(1)
+    lens = np.concatenate([np.arange(300), rng.integers(0, 20000, 200)])
+    aads = rng.integers(0, 40, 500)
+    seqs = rng.integers(0, 2**64, 500, dtype=np.uint64)
+    keys = np.sort(rng.integers(0, 7, 500))
+    b = RecordBatch.build_offsets(lens, aads, seqs, keys, in_base=5, out_base=3, aad_base=1, in_place=in_place)
+    s, o = b.seal, b.open
+    assert (s["len"] == lens).all() and (s["aad_len"] == aads).all() and (s["seq"] == seqs).all() and (s["key_idx"] == keys).all()
+    assert s["out_off"][0] == 3 and s["aad_off"][0] == 1 and s["in_off"][0] == (3 if in_place else 5)
+    assert (s["out_off"][1:] == s["out_off"][:-1] + s["len"][:-1] + 16).all()
+    assert (s["aad_off"][1:] == s["aad_off"][:-1] + s["aad_len"][:-1]).all()
+    if in_place:
+        assert (s["in_off"] == s["out_off"]).all() and b.pt_bytes == b.sealed_bytes
+    else:
+        assert (s["in_off"][1:] == s["in_off"][:-1] + s["len"][:-1]).all()
+        assert b.pt_bytes >= int(s["in_off"][-1] + s["len"][-1]) + 64
+    assert b.sealed_bytes >= int(s["out_off"][-1] + s["len"][-1]) + 16 + 64
+    assert b.aad_bytes >= int(s["aad_off"][-1]) + int(s["aad_len"][-1]) + 64
+    # no two records share a byte: the covered bytes number exactly the sum of the sizes
+    cover = np.zeros(b.sealed_bytes, np.uint8)
+    for r in s:
+        cover[int(r["out_off"]):int(r["out_off"]) + int(r["len"]) + 16] += 1
+    assert cover.max() == 1 and int(cover.sum()) == int(lens.sum()) + 16 * 500
+    assert not cover[:3].any() and not cover[-64:].any()
+    assert {int(x) % 16 for x in s["out_off"]} == set(range(16))  # (the residues an aligned layout never reaches)
+    assert (o["in_off"] == s["out_off"]).all() and (o["out_off"] == s["in_off"]).all()
+    for f in ("seq", "aad_off", "len", "key_idx", "aad_len", "flags"):
+        assert (o[f] == s[f]).all()
+    assert b.n == 500 and b.payload_bytes == int(lens.sum())
+
+
+def test_packed_layout_empty_and_defaults():
+    b = RecordBatch.build_offsets([], [])
+    assert b.n == 0 and b.pt_bytes >= 64 and b.sealed_bytes >= 64 and b.aad_bytes >= 64
+    b = RecordBatch.build_offsets([7, 0, 9], 2)
+    assert b.seal["in_off"].tolist() == [0, 7, 7] and b.seal["out_off"].tolist() == [0, 23, 39]
+    assert b.seal["aad_off"].tolist() == [0, 2, 4] and b.seal["seq"].tolist() == [0, 1, 2]
+
+
 def test_algorithmic_bytes():
     # SURVEY.md §8(d): per record seal+open = 4L + 2A + 32 (+ 2 descriptors, + ok byte)
     lens, aads = np.array([16384]), np.array([5])
