@@ -374,13 +374,19 @@ def seal_batch_hp(ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, aad_ptr: i
         raise _err("ptls_mi355x_seal_batch_hp")
 
 
+def _quic_packets(name: str, ks_handle, hp_ks, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, stream: int, *open_ptrs: int) -> None:
+    """The C call `name` of the four QUIC packet calls: ks's handle as the caller passes it, hp_ks (None travels as NULL,
+    which the engine refuses), and for an open ok and results between out and stream."""
+    if getattr(load_library(), name)(ks_handle, hp_ks.handle if hp_ks is not None else None, recs_ptr, nrecs, in_ptr, out_ptr,
+                                     *(p or None for p in open_ptrs), stream or None) != 0:
+        raise _err(name)
+
+
 def seal_quic_packets(ks: Keyset, hp_ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, stream: int = 0) -> None:
     """QUIC packet protection under AES-GCM (RFC 9001 5.3-5.4) in one call: cleartext header || payload at in + in_off
     (aad_len header bytes, len payload bytes, seq the full packet number) to protected header || ciphertext || tag at
     out + out_off, the mask AES-ECB(hp_ks key, sample); device pointers."""
-    if load_library().ptls_mi355x_seal_quic_packets(ks.handle if ks is not None else None, hp_ks.handle if hp_ks is not None else None,
-                                                    recs_ptr, nrecs, in_ptr, out_ptr, stream or None) != 0:
-        raise _err("ptls_mi355x_seal_quic_packets")
+    _quic_packets("ptls_mi355x_seal_quic_packets", ks.handle if ks is not None else None, hp_ks, recs_ptr, nrecs, in_ptr, out_ptr, stream)
 
 
 def open_quic_packets(ks: Keyset, hp_ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int, ok_ptr: int,
@@ -389,10 +395,8 @@ def open_quic_packets(ks: Keyset, hp_ks: Keyset, recs_ptr: int, nrecs: int, in_p
     the bytes from there to the packet's end, seq the expected packet number, flags bit 0 the expected key phase):
     unprotected header || plaintext to out + out_off, QUIC_RESULT_DTYPE results (both ok and results are required);
     device pointers."""
-    if load_library().ptls_mi355x_open_quic_packets(ks.handle if ks is not None else None, hp_ks.handle if hp_ks is not None else None,
-                                                    recs_ptr, nrecs, in_ptr, out_ptr, ok_ptr or None, results_ptr or None,
-                                                    stream or None) != 0:
-        raise _err("ptls_mi355x_open_quic_packets")
+    _quic_packets("ptls_mi355x_open_quic_packets", ks.handle if ks is not None else None, hp_ks, recs_ptr, nrecs, in_ptr, out_ptr, stream,
+                  ok_ptr, results_ptr)
 
 
 def quiclb_batch(ks: Keyset, cids_ptr: int, n: int, in_ptr: int, out_ptr: int, stream: int = 0) -> None:
@@ -495,9 +499,7 @@ def chacha_seal_quic_packets(ks: ChaChaKeyset, hp_ks: ChaChaKeyset, recs_ptr: in
                              stream: int = 0) -> None:
     """QUIC packet protection (RFC 9001 5.3-5.4) in one launch: cleartext header || payload at in + in_off (aad_len header
     bytes, len payload bytes, seq the full packet number) to protected header || ciphertext || tag; device pointers."""
-    if load_library().ptls_mi355x_chacha_seal_quic_packets(ks.handle, hp_ks.handle if hp_ks is not None else None, recs_ptr, nrecs,
-                                                           in_ptr, out_ptr, stream or None) != 0:
-        raise _err("ptls_mi355x_chacha_seal_quic_packets")
+    _quic_packets("ptls_mi355x_chacha_seal_quic_packets", ks.handle, hp_ks, recs_ptr, nrecs, in_ptr, out_ptr, stream)
 
 
 def chacha_open_quic_packets(ks: ChaChaKeyset, hp_ks: ChaChaKeyset, recs_ptr: int, nrecs: int, in_ptr: int, out_ptr: int,
@@ -505,9 +507,7 @@ def chacha_open_quic_packets(ks: ChaChaKeyset, hp_ks: ChaChaKeyset, recs_ptr: in
     """Removes header protection and opens protected QUIC packets (aad_len the packet-number offset, len the bytes from
     there to the packet's end, seq the expected packet number, flags bit 0 the expected key phase): unprotected header ||
     plaintext to out + out_off, QUIC_RESULT_DTYPE results (both ok and results are required); device pointers."""
-    if load_library().ptls_mi355x_chacha_open_quic_packets(ks.handle, hp_ks.handle if hp_ks is not None else None, recs_ptr, nrecs,
-                                                           in_ptr, out_ptr, ok_ptr or None, results_ptr or None, stream or None) != 0:
-        raise _err("ptls_mi355x_chacha_open_quic_packets")
+    _quic_packets("ptls_mi355x_chacha_open_quic_packets", ks.handle, hp_ks, recs_ptr, nrecs, in_ptr, out_ptr, stream, ok_ptr, results_ptr)
 
 
 def chacha_debug_poly1305(key32: bytes, msg: bytes) -> bytes:

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <type_traits>
@@ -55,6 +56,7 @@
 #include "engine/record.h"
 #include "engine/segment.h"
 #include "engine/gcm_kernels.h"
+#include "quic/header.h"  // (suite-neutral: the ChaCha20 kernels below use it too)
 #include "engine/aux_kernels.h"
 #include "engine/span_kernels.h"
 

@@ -25,11 +25,13 @@ struct st_ptls_mi355x_chacha_keyset_t {
 
 static std::atomic<u32> g_chacha_force_g{0}, g_chacha_force_wgs{0};
 
-// `launch()` on `s` and the keyset's use after it (ks->mu held); a launch error is reported through `fmt`
+// `launch()` on `s` and the keyset's use after it (ks->mu held); a launch error is reported through `fmt`. A launch that
+// reads a second keyset too (QUIC packets: `hp_ks`, its mutex held as well) is a use of both.
 template <typename Launch>
-static int chacha_launch_noted(ptls_mi355x_chacha_keyset_t *ks, hipStream_t s, const char *fmt, Launch launch)
+static int chacha_launch_noted(ptls_mi355x_chacha_keyset_t *ks, hipStream_t s, const char *fmt, Launch launch,
+                               ptls_mi355x_chacha_keyset_t *hp_ks = nullptr)
 {
-    return launch_and_note(ks->uses, ks->ds, s, [&] {
+    return launch_and_note_both(ks, hp_ks != nullptr ? hp_ks : ks, s, [&] {
         LAUNCH_CLEAR();
         launch();
         const hipError_t e = hipGetLastError();
@@ -91,25 +93,18 @@ static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int f
 }
 
 // QUIC packets: one launch (seal), or the header pre-pass and the batch behind it on the same stream (open). The launch
-// reads both keysets, so it is a use of both: a free or rekey of either orders itself behind it. Two distinct keysets'
-// mutexes are taken in the order of their addresses, whichever role each has in this call.
+// reads both keysets: PairLock and launch_and_note_both (host/runtime.h).
 static int chacha_launch_quic(ptls_mi355x_chacha_keyset_t *ks, ptls_mi355x_chacha_keyset_t *hp_ks, bool open,
                               const ptls_mi355x_record_t *recs, size_t nrecs, const void *in, void *out, uint8_t *ok,
                               ptls_mi355x_quic_result_t *results, void *stream)
 {
-    if (ks == NULL || hp_ks == NULL ||
-        (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && (ok == NULL || results == NULL)))))
-        return fail("%s", "chacha quic packets: invalid arguments");
-    if (hp_ks->device != ks->device)
-        return fail("%s", "chacha quic packets: hp_ks is on another device than ks");
+    if (check_quic_args("chacha quic packets", ks, hp_ks, open, recs, nrecs, in, out, ok, results) != 0)
+        return -1;
     if (nrecs == 0)
         return 0;
     DeviceScope scope(ks->device);
     hipStream_t s = (hipStream_t)stream;
-    const bool ks_first = std::less<ptls_mi355x_chacha_keyset_t *>()(ks, hp_ks);
-    std::unique_lock<std::mutex> lk1((ks_first ? ks : hp_ks)->mu), lk2;
-    if (hp_ks != ks)
-        lk2 = std::unique_lock<std::mutex>((ks_first ? hp_ks : ks)->mu);
+    PairLock<ptls_mi355x_chacha_keyset_t> locks(ks, hp_ks);
     const unsigned *slot = ks->slots.get(s, ks->uses, [&](unsigned &i) { return i = (unsigned)ks->slots.v.size(), true; });
     if (slot == nullptr)
         return -1;
@@ -119,15 +114,11 @@ static int chacha_launch_quic(ptls_mi355x_chacha_keyset_t *ks, ptls_mi355x_chach
     a.claim = ks->d_claim + 2 * *slot;
     a.hp_keys = hp_ks->d_keys, a.hp_nkeys = (u32)hp_ks->nkeys, a.results = results;
     const unsigned grid = chacha_grid(ks->ds, nrecs);
-    const auto launch = [&] {
-        return chacha_launch_noted(ks, s, "chacha quic packets launch: %s", [&] {
-            if (open)
-                chacha_quic_unmask_kernel<<<aux_grid(nrecs, ks->ds->ncu), 256, 0, s>>>(a.hp_keys, a.hp_nkeys, a.nkeys, recs, nrecs, a.in,
-                                                                                     results);
-            chacha_launch_kernel(open, 2, grid, s, a);
-        });
-    };
-    return hp_ks != ks ? launch_and_note(hp_ks->uses, hp_ks->ds, s, launch) : launch();
+    return chacha_launch_noted(ks, s, "chacha quic packets launch: %s", [&] {
+        if (open)
+            chacha_quic_unmask_kernel<<<aux_grid(nrecs, ks->ds->ncu), 256, 0, s>>>(a.hp_keys, a.hp_nkeys, a.nkeys, recs, nrecs, a.in, results);
+        chacha_launch_kernel(open, 2, grid, s, a);
+    }, hp_ks);
 }
 
 extern "C" {

@@ -68,8 +68,8 @@ __device__ __forceinline__ void quic_protect_header(const ChaChaArgs &a, const p
     chacha20_block(key, sample.x, sample.y, sample.z, sample.w, x);
     const uint8_t *pin = a.in + r.in_off + r.aad_len - pn_len;
     uint8_t *hout = a.out + r.out_off, *pout = hout + r.aad_len - pn_len;
-    const u32 m14 = x[0] >> 8 | x[1] << 24;  // mask[1 .. 4]
-    hout[0] = (uint8_t)(first ^ (x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu)));
+    const u32 m14 = quic_m14(x[0], x[1]);
+    hout[0] = (uint8_t)(first ^ (x[0] & quic_first_mask(first)));
 #pragma unroll
     for (u32 i = 0; i < 4; ++i) {
         if (i < pn_len)
@@ -93,19 +93,17 @@ __device__ __forceinline__ void chacha_record(const ChaChaArgs &a, u64 idx, u32 
     [[maybe_unused]] bool quic_good = false;
     if constexpr (FRAME == 2) {
         if constexpr (OPEN) {
-            u32x4 q = {0, 0, 0, (u32)PTLS_MI355X_QUIC_REJECTED << 16};
+            u32x4 q = {0, 0, 0, QUIC_RESULT_REJECTED_W};
             if (valid)
                 q = *(const u32x4_u *)(a.results + idx);
-            r.seq = (u64)q.x | (u64)q.y << 32, quic_len = q.z, pn_len = q.w & 0xff, first = (q.w >> 8) & 0xff;
-            quic_good = valid && ((q.w >> 16) & 0xff) == PTLS_MI355X_QUIC_OK;
+            r.seq = quic_result_pn(q), quic_len = quic_result_payload_len(q), pn_len = quic_result_pn_len(q), first = quic_result_first(q);
+            quic_good = valid && quic_result_status(q) == PTLS_MI355X_QUIC_OK;
         } else {
-            quic_good = valid && r.aad_len >= 2 && r.flags == 0 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.key_idx < a.nkeys &&
-                        r.key_idx < a.hp_nkeys;
+            quic_good = quic_seal_admits(r, a.nkeys, a.hp_nkeys);  // (a lane without a packet: r is zero, which this refuses)
             if (quic_good)
                 first = a.in[r.in_off];
-            pn_len = (first & 3) + 1, quic_len = r.len;
-            // the header holds a byte before the packet number, and packet number and payload cover a sample's first 4 bytes
-            quic_good = quic_good && r.aad_len >= 1 + pn_len && pn_len + r.len >= 4;
+            pn_len = quic_pn_len(first), quic_len = r.len;
+            quic_good = quic_good && quic_seal_admits_pn(r, pn_len);
         }
     }
     const u32 A = FRAME == 1 ? (u32)TLS_HEADER_SIZE : FRAME == 2 ? r.aad_len + (OPEN ? pn_len : 0u) : PTLS_MI355X_RECORD_AAD_LEN(&r);
@@ -465,9 +463,8 @@ __global__ __launch_bounds__(256) void chacha_quic_unmask_kernel(const ChaChaKey
 {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
         const ptls_mi355x_record_t r = recs[i];
-        u32x4 res = {0, 0, 0, (u32)PTLS_MI355X_QUIC_REJECTED << 16};
-        // len: the packet number, the ciphertext and the tag; 4 + 16 of them are the sample's bytes at the least
-        if (r.len >= 20 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.aad_len >= 1 && r.key_idx < nkeys && r.key_idx < hp_nkeys) {
+        u32x4 res = quic_result_rejected();
+        if (quic_open_admits(r, nkeys, hp_nkeys)) {
             const uint8_t *p = in + r.in_off, *pn = p + r.aad_len;
             const u32x4 s = *(const u32x4_u *)(pn + 4);
             const ChaChaKey *ke = hp_keys + r.key_idx;
@@ -476,25 +473,8 @@ __global__ __launch_bounds__(256) void chacha_quic_unmask_kernel(const ChaChaKey
             for (int k = 0; k < 8; ++k)
                 key[k] = ke->key[k];
             chacha20_block(key, s.x, s.y, s.z, s.w, x);
-            u32 first = p[0];
-            first ^= x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu);
-            const u32 pn_len = (first & 3) + 1, m14 = x[0] >> 8 | x[1] << 24;  // mask[1 .. 4]
-            u32 trunc = 0;
-#pragma unroll
-            for (u32 k = 0; k < 4; ++k) {
-                if (k < pn_len)
-                    trunc = trunc << 8 | (((u32)pn[k] ^ (m14 >> (8 * k))) & 0xff);
-            }
-            // RFC 9000 A.3: the candidate in the expected number's window, moved a window up or down when that is closer
-            const u64 win = 1ull << (8 * pn_len), hwin = win >> 1;
-            u64 cand = (r.seq & ~(win - 1)) | trunc;
-            if (cand + hwin <= r.seq && cand < (1ull << 62) - win)
-                cand += win;
-            else if (cand > r.seq + hwin && cand >= win)
-                cand -= win;
-            const bool phase = (first & 0x80) == 0 && ((first >> 2) & 1) != (r.flags & 1u);
-            res.x = (u32)cand, res.y = (u32)(cand >> 32), res.z = r.len - pn_len - 16;
-            res.w = pn_len | first << 8 | (u32)(phase ? PTLS_MI355X_QUIC_KEY_PHASE : PTLS_MI355X_QUIC_OK) << 16;
+            const QuicUnmasked u = quic_unmask(p[0], pn, x[0], quic_m14(x[0], x[1]), r.seq, r.flags);
+            res = quic_result_pack(u, r.len - u.pn_len - 16);
         }
         *(u32x4_u *)(results + i) = res;
     }

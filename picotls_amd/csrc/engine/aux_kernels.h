@@ -359,34 +359,28 @@ __global__ __launch_bounds__(QUIC_AUX_WG) void quic_unmask_kernel(const KeyEntry
     const u32 laneoff = (threadIdx.x & 31) * 4;
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
         const ptls_mi355x_record_t r = recs[i];
-        u32x4 res = {0, 0, 0, (u32)PTLS_MI355X_QUIC_REJECTED << 16};
+        u32x4 res = quic_result_rejected();
         bool pass = false;
         u32 A = 0, T = 0;
         u64 pnum = 0;
-        // len: the packet number, the ciphertext and the tag; 4 + 16 of them are the sample's bytes at the least
-        if (r.len >= 20 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.aad_len >= 1 && r.key_idx < nkeys && r.key_idx < hp_nkeys) {
+        // quic_unmask (quic/header.h) from its parts, the packet-number bytes read here: through quic_unmask itself this
+        // kernel takes one more VGPR (76 and 79 for 75 and 78), and its figures are held equal
+        if (quic_open_admits(r, nkeys, hp_nkeys)) {
             const uint8_t *p = in + r.in_off, *pn = p + r.aad_len;
             const u32x4 x = quic_mask<NR>(lds, laneoff, hp_keys + r.key_idx, *(const u32x4_u *)(pn + 4));
             u32 first = p[0];
-            first ^= x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu);
-            const u32 pn_len = (first & 3) + 1, m14 = x[0] >> 8 | x[1] << 24;  // mask[1 .. 4]
+            first ^= x[0] & quic_first_mask(first);
+            const u32 pn_len = quic_pn_len(first), m14 = quic_m14(x[0], x[1]);
             u32 trunc = 0;
 #pragma unroll
             for (u32 k = 0; k < 4; ++k) {
                 if (k < pn_len)
                     trunc = trunc << 8 | (((u32)pn[k] ^ (m14 >> (8 * k))) & 0xff);
             }
-            // RFC 9000 A.3: the candidate in the expected number's window, moved a window up or down when that is closer
-            const u64 win = 1ull << (8 * pn_len), hwin = win >> 1;
-            u64 cand = (r.seq & ~(win - 1)) | trunc;
-            if (cand + hwin <= r.seq && cand < (1ull << 62) - win)
-                cand += win;
-            else if (cand > r.seq + hwin && cand >= win)
-                cand -= win;
-            const bool phase = (first & 0x80) == 0 && ((first >> 2) & 1) != (r.flags & 1u);
+            const u64 cand = quic_decode_pn(r.seq, trunc, pn_len);
+            const bool phase = quic_key_phase_differs(first, r.flags);
             A = (u32)r.aad_len + pn_len, T = r.len - pn_len - 16, pnum = cand, pass = !phase;
-            res.x = (u32)cand, res.y = (u32)(cand >> 32), res.z = T;
-            res.w = pn_len | first << 8 | (u32)(phase ? PTLS_MI355X_QUIC_KEY_PHASE : PTLS_MI355X_QUIC_OK) << 16;
+            res = quic_result_pack(QuicUnmasked{first, pn_len, cand, phase}, T);
             if (pass)
                 quic_put_header(out + r.out_off, p, A, first ^ p[0], pn_len, m14);
         }
@@ -402,11 +396,9 @@ __global__ __launch_bounds__(256) void quic_seal_check_kernel(u32 hp_nkeys, u32 
 {
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
         const ptls_mi355x_record_t r = recs[i];
-        bool pass = r.aad_len >= 2 && r.flags == 0 && r.len <= PTLS_MI355X_MAX_RECORD_LEN && r.key_idx < nkeys && r.key_idx < hp_nkeys;
-        if (pass) {
-            const u32 pn_len = ((u32)in[r.in_off] & 3) + 1;
-            pass = r.aad_len >= 1 + pn_len && pn_len + r.len >= 4;
-        }
+        bool pass = quic_seal_admits(r, nkeys, hp_nkeys);
+        if (pass)
+            pass = quic_seal_admits_pn(r, quic_pn_len(in[r.in_off]));
         quic_put_desc(desc + i, r, pass, r.aad_len, r.len, r.seq);
     }
 }
@@ -429,9 +421,9 @@ __global__ __launch_bounds__(QUIC_AUX_WG) void quic_protect_kernel(const KeyEntr
             continue;
         const uint8_t *p = in + d.in_off;
         uint8_t *o = out + d.out_off;
-        const u32 A = d.aad_len, first = p[0], pn_len = (first & 3) + 1;
+        const u32 A = d.aad_len, first = p[0], pn_len = quic_pn_len(first);
         const u32x4 x = quic_mask<NR>(lds, laneoff, hp_keys + d.key_idx, *(const u32x4_u *)(o + A - pn_len + 4));
-        quic_put_header(o, p, A, x[0] & ((first & 0x80) != 0 ? 0x0fu : 0x1fu), pn_len, x[0] >> 8 | x[1] << 24);
+        quic_put_header(o, p, A, x[0] & quic_first_mask(first), pn_len, quic_m14(x[0], x[1]));
     }
 }
 

@@ -923,32 +923,19 @@ static int launch_hp(const KeyEntry *keys, u32 nkeys, int nr, int ncu, const ptl
 // QUIC packets (ptls_mi355x_seal_quic_packets / ptls_mi355x_open_quic_packets): the pre-pass, the FRAME 3 batch on the
 // descriptors it wrote, the finish kernel (aux_kernels.h), all on `stream` with no host work between them. The
 // descriptors live in ks's scratch (d_quic), so ks->mu is held from taking it through the last launch and the use event
-// after it. The launches read both keysets, so the call is a use of both: a free or rekey of either orders itself
-// behind it. Two distinct keysets' mutexes are taken in the order of their addresses, whichever role each has here.
+// after it. The launches read both keysets: PairLock and launch_and_note_both (host/runtime.h).
 static int launch_quic(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, bool open, const ptls_mi355x_record_t *recs,
                        size_t nrecs, const void *in, void *out, uint8_t *ok, ptls_mi355x_quic_result_t *results, void *stream)
 {
-    if (ks == NULL || hp_ks == NULL ||
-        (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && (ok == NULL || results == NULL)))))
-        return fail("%s", "quic packets: invalid arguments");
-    if (hp_ks->device != ks->device)
-        return fail("%s", "quic packets: hp_ks is on another device than ks");
+    if (check_quic_args("quic packets", ks, hp_ks, open, recs, nrecs, in, out, ok, results) != 0)
+        return -1;
     if (nrecs == 0)
         return 0;
     DeviceScope scope(ks->device);
     hipStream_t s = (hipStream_t)stream;
     if (wait_ready(ks, s) != 0 || (hp_ks != ks && wait_ready(hp_ks, s) != 0))
         return -1;
-    const bool ks_first = hp_ks == ks || std::less<ptls_mi355x_keyset_t *>()(ks, hp_ks);
-    std::unique_lock<std::mutex> lk(ks->mu, std::defer_lock), lkh;
-    if (hp_ks != ks)
-        lkh = std::unique_lock<std::mutex>(hp_ks->mu, std::defer_lock);
-    if (ks_first)
-        lk.lock();
-    if (hp_ks != ks)
-        lkh.lock();
-    if (!ks_first)
-        lk.lock();
+    PairLock<ptls_mi355x_keyset_t> locks(ks, hp_ks);
     // the descriptor scratch: after its last user on another stream, grown in stream order on this one
     if (ks->quic_used && ks->quic_stream != s) {
         const hipEvent_t last = ks->uses.event_of(ks->quic_stream);
@@ -967,31 +954,28 @@ static int launch_quic(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, bo
     const unsigned grid = aux_grid(nrecs, ks->ds->ncu);
     // (the kernels with the AES tables in LDS: two workgroups of QUIC_AUX_WG threads a CU)
     const unsigned lgrid = (unsigned)min((u64)(nrecs + QUIC_AUX_WG - 1) / QUIC_AUX_WG, (u64)ks->ds->ncu * 2);
-    const auto launch = [&] {
-        return launch_and_note(ks->uses, ks->ds, s, [&] {
-            LAUNCH_CLEAR();
-            if (open)
-                with_nr(hp_ks->nr, [&](auto NR) {
-                    quic_unmask_kernel<NR><<<lgrid, QUIC_AUX_WG, LDS_AES_BYTES, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, (u32)ks->nkeys, recs, nrecs,
-                                                                           (const uint8_t *)in, (uint8_t *)out, results, desc);
-                });
-            else
-                quic_seal_check_kernel<<<grid, 256, 0, s>>>((u32)hp_ks->nkeys, (u32)ks->nkeys, recs, nrecs, (const uint8_t *)in, desc);
-            HIP_TRY(hipGetLastError());
-            if (launch_batch(ks, open, desc, nrecs, in, NULL, out, ok, stream, 3, nullptr, &lk) != 0)
-                return -1;
-            LAUNCH_CLEAR();
-            if (open)
-                quic_status_kernel<<<grid, 256, 0, s>>>(ok, results, nrecs);
-            else
-                with_nr(hp_ks->nr, [&](auto NR) {
-                    quic_protect_kernel<NR><<<lgrid, QUIC_AUX_WG, LDS_AES_BYTES, s>>>(hp_ks->d_keys, desc, nrecs, (const uint8_t *)in, (uint8_t *)out);
-                });
-            HIP_TRY(hipGetLastError());
-            return 0;
-        });
-    };
-    return hp_ks != ks ? launch_and_note(hp_ks->uses, hp_ks->ds, s, launch) : launch();
+    return launch_and_note_both(ks, hp_ks, s, [&] {
+        LAUNCH_CLEAR();
+        if (open)
+            with_nr(hp_ks->nr, [&](auto NR) {
+                quic_unmask_kernel<NR><<<lgrid, QUIC_AUX_WG, LDS_AES_BYTES, s>>>(hp_ks->d_keys, (u32)hp_ks->nkeys, (u32)ks->nkeys, recs, nrecs,
+                                                                       (const uint8_t *)in, (uint8_t *)out, results, desc);
+            });
+        else
+            quic_seal_check_kernel<<<grid, 256, 0, s>>>((u32)hp_ks->nkeys, (u32)ks->nkeys, recs, nrecs, (const uint8_t *)in, desc);
+        HIP_TRY(hipGetLastError());
+        if (launch_batch(ks, open, desc, nrecs, in, NULL, out, ok, stream, 3, nullptr, &locks.ks_lock) != 0)
+            return -1;
+        LAUNCH_CLEAR();
+        if (open)
+            quic_status_kernel<<<grid, 256, 0, s>>>(ok, results, nrecs);
+        else
+            with_nr(hp_ks->nr, [&](auto NR) {
+                quic_protect_kernel<NR><<<lgrid, QUIC_AUX_WG, LDS_AES_BYTES, s>>>(hp_ks->d_keys, desc, nrecs, (const uint8_t *)in, (uint8_t *)out);
+            });
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 extern "C" {

@@ -1,6 +1,7 @@
 // picotls_amd/csrc/host/runtime.h -- the host runtime both AEAD families share: error reporting, the per-device state
 // and its pools (events, one-key slab entries, staging buffers), the synchronous staging round trip, the record of a
-// keyset's launches (StreamUses), per-stream slots (StreamSlots) and the run-time -> template dispatch helpers.
+// keyset's launches (StreamUses), per-stream slots (StreamSlots), the run-time -> template dispatch helpers and what a
+// call on two keysets needs (QUIC packets: argument check, PairLock, launch_and_note_both).
 // Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip (included after the device code; not standalone).
 #ifndef PTLS_MI355X_HOST_RUNTIME_H
 #define PTLS_MI355X_HOST_RUNTIME_H
@@ -661,6 +662,47 @@ static int check_single_args(const char *what, bool key_ok, const void *aad, siz
         return fail("%s: invalid arguments", what);
     if (len > PTLS_MI355X_MAX_RECORD_LEN || aadlen > PTLS_MI355X_MAX_AAD_LEN)
         return fail("%s: record or AAD longer than PTLS_MI355X_MAX_RECORD_LEN / PTLS_MI355X_MAX_AAD_LEN", what);
+    return 0;
+}
+
+// ---- calls on two keysets of one family (QUIC packets: `ks` holds the AEAD keys, `hp_ks` the header-protection keys;
+// they may be one object). KS has `mu`, `uses`, `ds` and `device`.
+// Both keysets' mutexes, two distinct ones taken in the order of their addresses, whichever role each has in the call
+template <typename KS>
+struct PairLock {
+    std::unique_lock<std::mutex> ks_lock, hp_lock;  // (hp_lock: empty when hp_ks is ks)
+    PairLock(KS *ks, KS *hp_ks) : ks_lock(ks->mu, std::defer_lock)
+    {
+        if (hp_ks != ks)
+            hp_lock = std::unique_lock<std::mutex>(hp_ks->mu, std::defer_lock);
+        const bool ks_first = hp_ks == ks || std::less<KS *>()(ks, hp_ks);
+        if (ks_first)
+            ks_lock.lock();
+        if (hp_ks != ks)
+            hp_lock.lock();
+        if (!ks_first)
+            ks_lock.lock();
+    }
+};
+
+// `launch()` on `s` as a use of both keysets (both mutexes held): a free or rekey of either orders itself behind it
+template <typename KS, typename Launch>
+static int launch_and_note_both(KS *ks, KS *hp_ks, hipStream_t s, Launch launch)
+{
+    const auto on_ks = [&] { return launch_and_note(ks->uses, ks->ds, s, launch); };
+    return hp_ks != ks ? launch_and_note(hp_ks->uses, hp_ks->ds, s, on_ks) : on_ks();
+}
+
+// a QUIC packet call's arguments (results: the open's only)
+template <typename KS>
+static int check_quic_args(const char *what, const KS *ks, const KS *hp_ks, bool open, const void *recs, size_t nrecs,
+                           const void *in, const void *out, const void *ok, const void *results)
+{
+    if (ks == NULL || hp_ks == NULL ||
+        (nrecs != 0 && (recs == NULL || in == NULL || out == NULL || (open && (ok == NULL || results == NULL)))))
+        return fail("%s: invalid arguments", what);
+    if (hp_ks->device != ks->device)
+        return fail("%s: hp_ks is on another device than ks", what);
     return 0;
 }
 

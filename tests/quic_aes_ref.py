@@ -1,5 +1,5 @@
-"""Reference for QUIC packet protection under AES-GCM (RFC 9001 §5.3-5.4, RFC 9000 A.3), with the signatures of
-quic_ref (its ChaCha20 counterpart). Two independent sources behind ``impl``:
+"""Reference for QUIC packet protection under AES-GCM (RFC 9001 §5.3-5.4, RFC 9000 A.3): the AES primitives, bound to
+quic_ref's protect and unprotect under that module's names and signatures. Two independent sources behind ``impl``:
 
   "ossl"    AES-GCM and AES-ECB of the system libcrypto through ctypes (EVP_aes_{128,256}_gcm, EVP_aes_{128,256}_ecb),
             found the way chacha_ref finds it;
@@ -12,9 +12,11 @@ both sources, so the two sources are checked against each other instead (test_qu
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import chacha_ref as R
-from quic_ref import BAD_MAC, KEY_PHASE, OK, REJECTED, Opened, decode_pn  # noqa: F401
+import quic_ref
+from quic_ref import BAD_MAC, KEY_PHASE, OK, REJECTED, Opened, _apply_mask, decode_pn  # noqa: F401
 
 _oracle = None
 _evp_ready = False
@@ -116,42 +118,8 @@ def hp_mask(hp: bytes, sample: bytes, impl: str = "ossl") -> bytes:
     return ossl_aes_ecb(hp, sample)[:5]
 
 
-def _apply_mask(first: int, mask: bytes) -> int:
-    return first ^ (mask[0] & (0x0f if first & 0x80 else 0x1f))
-
-
-def protect(key: bytes, iv: bytes, hp: bytes, pn: int, header: bytes, payload: bytes, impl: str = "ossl") -> bytes:
-    """header (cleartext, ending in the truncated packet number of (header[0] & 3) + 1 bytes) || payload to the protected
-    packet: header' || ciphertext || tag."""
-    pn_len = (header[0] & 3) + 1
-    assert len(header) >= 1 + pn_len and pn_len + len(payload) >= 4
-    sealed = gcm_seal(key, iv, pn, header, payload, impl)
-    pn_off = len(header) - pn_len
-    sample = (header[pn_off:] + sealed)[4:20]
-    mask = hp_mask(hp, sample, impl)
-    out = bytearray(header)
-    out[0] = _apply_mask(header[0], mask)
-    for i in range(pn_len):
-        out[pn_off + i] ^= mask[1 + i]
-    return bytes(out) + sealed
-
-
-def unprotect(key: bytes, iv: bytes, hp: bytes, expected_pn: int, pn_off: int, packet: bytes, phase: int = 0,
-              impl: str = "ossl") -> Opened:
-    """The receiver's side: packet is the whole protected packet, pn_off the offset of its packet-number field."""
-    if pn_off < 1 or len(packet) - pn_off < 20:
-        return Opened(REJECTED)
-    mask = hp_mask(hp, packet[pn_off + 4:pn_off + 20], impl)
-    first = packet[0] ^ (mask[0] & (0x0f if packet[0] & 0x80 else 0x1f))  # (bit 7 is not protected)
-    pn_len = (first & 3) + 1
-    trunc = bytes(packet[pn_off + i] ^ mask[1 + i] for i in range(pn_len))
-    pn = decode_pn(expected_pn, int.from_bytes(trunc, "big"), pn_len)
-    header = bytes([first]) + packet[1:pn_off] + trunc
-    res = Opened(OK, pn, pn_len, first, header)
-    if not first & 0x80 and (first >> 2) & 1 != phase & 1:
-        res.status = KEY_PHASE
-        return res
-    res.payload = gcm_open(key, iv, pn, header, packet[pn_off + pn_len:], impl)
-    if res.payload is None:
-        res.status = BAD_MAC
-    return res
+AES_GCM = quic_ref.Suite(gcm_seal, gcm_open, hp_mask)
+# quic_ref's protect(key, iv, hp, pn, header, payload, impl="ossl") and unprotect(key, iv, hp, expected_pn, pn_off, packet,
+# phase=0, impl="ossl"), over AES-GCM and AES-ECB
+protect = functools.partial(quic_ref.protect, suite=AES_GCM)
+unprotect = functools.partial(quic_ref.unprotect, suite=AES_GCM)

@@ -1,6 +1,9 @@
-"""Reference for QUIC packet protection under ChaCha20-Poly1305 (RFC 9001 §5.3-5.4, RFC 9000 A.3), built only from what
-chacha_ref has: OpenSSL (ossl_seal / ossl_open / ossl_chacha20) and, as an independent second source, the plain-Python
-restatements (py_seal / py_open / py_chacha20_block). ``impl`` picks the source: "ossl" or "py".
+"""Reference for QUIC packet protection (RFC 9001 §5.3-5.4, RFC 9000 A.3): protect and unprotect, written once over a
+Suite (an AEAD seal and open and a header-protection mask), decode_pn, Opened and the statuses.
+
+The module's own names are the ChaCha20-Poly1305 binding, built only from what chacha_ref has: OpenSSL (ossl_seal /
+ossl_open / ossl_chacha20) and, as an independent second source, the plain-Python restatements (py_seal / py_open /
+py_chacha20_block). ``impl`` picks the source: "ossl" or "py". quic_aes_ref binds the same functions to AES-GCM.
 
 Statuses are those of include/picotls/mi355x.h (PTLS_MI355X_QUIC_*)."""
 from __future__ import annotations
@@ -8,6 +11,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass
+from typing import Callable
 
 import chacha_ref as R
 
@@ -29,8 +33,27 @@ def hp_mask(hp: bytes, sample: bytes, impl: str = "ossl") -> bytes:
     return R.ossl_chacha20(hp, sample, bytes(5))
 
 
+def _seal(key: bytes, iv: bytes, seq: int, aad: bytes, pt: bytes, impl: str = "ossl") -> bytes:
+    return (R.py_seal if impl == "py" else R.ossl_seal)(key, R.nonce_for(iv, seq), pt, aad)
+
+
+def _open(key: bytes, iv: bytes, seq: int, aad: bytes, sealed: bytes, impl: str = "ossl") -> bytes | None:
+    return (R.py_open if impl == "py" else R.ossl_open)(key, R.nonce_for(iv, seq), sealed, aad)
+
+
+@dataclass(frozen=True)
+class Suite:
+    """What protect / unprotect take from a cipher suite, each with a trailing ``impl`` that picks the source."""
+    seal: Callable[..., bytes]            # (key, iv, seq, aad, pt, impl) -> ciphertext || tag, nonce = iv ^ BE64(seq)
+    open: Callable[..., "bytes | None"]   # (key, iv, seq, aad, sealed, impl) -> plaintext, None on a bad tag
+    hp_mask: Callable[..., bytes]         # (hp, sample, impl) -> mask[0 .. 4]
+
+
+CHACHA20 = Suite(_seal, _open, hp_mask)
+
+
 def _apply_mask(first: int, mask: bytes) -> int:
-    return first ^ (mask[0] & (0x0f if first & 0x80 else 0x1f))
+    return first ^ (mask[0] & (0x0f if first & 0x80 else 0x1f))  # (bit 7 is not protected)
 
 
 def decode_pn(expected_pn: int, truncated_pn: int, pn_len: int) -> int:
@@ -45,16 +68,16 @@ def decode_pn(expected_pn: int, truncated_pn: int, pn_len: int) -> int:
     return cand
 
 
-def protect(key: bytes, iv: bytes, hp: bytes, pn: int, header: bytes, payload: bytes, impl: str = "ossl") -> bytes:
+def protect(key: bytes, iv: bytes, hp: bytes, pn: int, header: bytes, payload: bytes, impl: str = "ossl",
+            suite: Suite = CHACHA20) -> bytes:
     """header (cleartext, ending in the truncated packet number of (header[0] & 3) + 1 bytes) || payload to the protected
     packet: header' || ciphertext || tag."""
     pn_len = (header[0] & 3) + 1
     assert len(header) >= 1 + pn_len and pn_len + len(payload) >= 4
-    seal = R.py_seal if impl == "py" else R.ossl_seal
-    sealed = seal(key, R.nonce_for(iv, pn), payload, header)
+    sealed = suite.seal(key, iv, pn, header, payload, impl)
     pn_off = len(header) - pn_len
     sample = (header[pn_off:] + sealed)[4:20]
-    mask = hp_mask(hp, sample, impl)
+    mask = suite.hp_mask(hp, sample, impl)
     out = bytearray(header)
     out[0] = _apply_mask(header[0], mask)
     for i in range(pn_len):
@@ -73,12 +96,12 @@ class Opened:
 
 
 def unprotect(key: bytes, iv: bytes, hp: bytes, expected_pn: int, pn_off: int, packet: bytes, phase: int = 0,
-              impl: str = "ossl") -> Opened:
+              impl: str = "ossl", suite: Suite = CHACHA20) -> Opened:
     """The receiver's side: packet is the whole protected packet, pn_off the offset of its packet-number field."""
     if pn_off < 1 or len(packet) - pn_off < 20:
         return Opened(REJECTED)
-    mask = hp_mask(hp, packet[pn_off + 4:pn_off + 20], impl)
-    first = packet[0] ^ (mask[0] & (0x0f if packet[0] & 0x80 else 0x1f))  # (bit 7 is not protected)
+    mask = suite.hp_mask(hp, packet[pn_off + 4:pn_off + 20], impl)
+    first = _apply_mask(packet[0], mask)
     pn_len = (first & 3) + 1
     trunc = bytes(packet[pn_off + i] ^ mask[1 + i] for i in range(pn_len))
     pn = decode_pn(expected_pn, int.from_bytes(trunc, "big"), pn_len)
@@ -87,8 +110,7 @@ def unprotect(key: bytes, iv: bytes, hp: bytes, expected_pn: int, pn_off: int, p
     if not first & 0x80 and (first >> 2) & 1 != phase & 1:
         res.status = KEY_PHASE
         return res
-    opn = R.py_open if impl == "py" else R.ossl_open
-    res.payload = opn(key, R.nonce_for(iv, pn), packet[pn_off + pn_len:], header)
+    res.payload = suite.open(key, iv, pn, header, packet[pn_off + pn_len:], impl)
     if res.payload is None:
         res.status = BAD_MAC
     return res

@@ -21,12 +21,13 @@ FIELDS = (("TotalSGPRs", "SGPRs"), ("VGPRs", "VGPRs"), ("AGPRs", "AGPRs"), ("Scr
 def parse(path: str) -> dict[str, dict[str, str]]:
     kernels: dict[str, dict[str, str]] = {}
     cur = None
+    where = r"remark: (?:\S+:\d+:\d+: )?"  # (with debug locations the remark names the kernel's file, line and column first)
     for line in open(path, errors="replace"):
-        m = re.search(r"remark: Function Name: (\S+)", line)
+        m = re.search(where + r"Function Name: (\S+)", line)
         if m:
             cur = kernels.setdefault(m.group(1), {})
             continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
+        m = re.search(where + r"\s*([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = m.group(2)
     return kernels
@@ -80,7 +81,8 @@ def main(argv: list[str]) -> int:
         print()
     if gone:
         print("Gone: " + ", ".join(demangle(gone).values()) + "\n")
-    print("New:\n\n" + header())
+    if added:
+        print("New:\n\n" + header())
     for n in sorted(added, key=names.get):
         print(row(names[n], new[n]))
     return 1 if changed or gone else 0

@@ -1,28 +1,35 @@
 #!/usr/bin/env python3
-"""QUIC packet protection in one ChaCha20-Poly1305 call against the two launches it replaces, device-resident.
+"""QUIC packet protection in one call against the launches it replaces, device-resident, for either suite.
 
-    python tools/chacha_quic_rate.py [--steps 20 --warmup 3 --rounds 5] [--shapes quic1200,quic2perkey] [--scale 1.0]
+    python tools/quic_rate.py --suite {aesgcm,chacha} [--steps 20 --warmup 3 --rounds 5] [--shapes quic1200,quic2perkey]
+                              [--scale 1.0]
 
 Timed the way tools/chacha_rate.py times: inputs already in HBM, the arms interleaved in one process (`rounds` times
 each arm in turn runs steps / rounds timed steps), the shader clock inside the batch kernels (workgroup 0 of every
 launch, ptls_mi355x_debug_kernel_clock) beside each rate. Seal and open are timed apart; a rate is payload bytes over
-wall time, GiB/s. Prints one JSON line.
+wall time, GiB/s. Prints one JSON line, whose "tool" is the name this suite's tool had while there was one per suite
+(chacha_quic_rate, aesgcm_quic_rate), so that results stay comparable.
 
 Arms, per direction:
   new        seal: ptls_mi355x_chacha_seal_quic_packets (protected header || ciphertext || tag, one launch)
+                   ptls_mi355x_seal_quic_packets (the descriptor pre-pass, the batch, the header-protection finish)
              open: ptls_mi355x_chacha_open_quic_packets (the unmasking pre-pass and the batch, no host work between)
-  old        seal: chacha_seal_batch, then chacha_hp_mask_batch on the sealed samples; the masks are left unapplied
-             open: chacha_hp_mask_batch, then chacha_open_batch on descriptors and unmasked headers that were prepared
+                   ptls_mi355x_open_quic_packets (the unmasking pre-pass, the batch, the status finish)
+  old        seal: chacha_seal_batch, then chacha_hp_mask_batch on the sealed samples
+                   ptls_mi355x_seal_batch_hp on an AAD arena prepared before timing
+                   (either way the masks are left unapplied)
+             open: the suite's hp_mask_batch, then its open_batch on descriptors and unmasked headers that were prepared
                    on the host before timing, so the host round trip a real receiver makes between the two is left out
   old_again  the old arm once more: the spread of two runs of the same code (A/A)
 Both omissions favour the old arm.
 
 Shapes: 1,048,576 x 1200 B under one key; 131,072 x 1200 B over 65,536 keys (2 a key, distinct header-protection keys).
-Packets have a short header: first byte, an 8-byte DCID, a packet number of 1..4 bytes.
+AES-GCM keys are AES-128. Packets have a short header: first byte, an 8-byte DCID, a packet number of 1..4 bytes.
 
 Bar: new >= old x (1 - spread) for seal and for open on either shape, spread = |old - old_again| / old ("bar_met").
-Measured (profiles/chacha20_quic.md, builder-box): new / old 1.000 (seal) and 0.995 (open) under one key, 0.992 and 0.981
-over 65,536 keys, A/A spread 0.0002-0.0010: the one-key seal meets the bar, the other three miss it by 0.5-1.9 %.
+Measured: profiles/chacha20_quic.md (builder-box: new / old 1.000 (seal) and 0.995 (open) under one key, 0.992 and 0.981
+over 65,536 keys, A/A spread 0.0002-0.0010: the one-key seal meets the bar, the other three miss it by 0.5-1.9 %) and
+profiles/aesgcm_quic.md.
 """
 from __future__ import annotations
 
@@ -48,12 +55,34 @@ DCID = 8
 ARMS = ("new", "old", "old_again")
 
 
-def run_shape(name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int, rounds: int) -> dict:
+def suite_calls(pa, suite: str) -> dict:
+    """what differs between the suites: the keyset of n keys, the five engine calls, the counters and the JSON's names"""
+    if suite == "chacha":
+        def seal_old(ks, hp_ks, recs, n, src, aad, out, hp, masks, sp):
+            pa.chacha_seal_batch(ks, recs, n, src, aad, out, sp)
+            pa.chacha_hp_mask_batch(hp_ks, hp, n, out, masks, sp)
+
+        return {"keyset": lambda rng, n, zero_iv: pa.ChaChaKeyset(rng.bytes(32 * n), bytes(12 * n) if zero_iv else rng.bytes(12 * n)),
+                "seal_new": pa.chacha_seal_quic_packets, "open_new": pa.chacha_open_quic_packets, "seal_old": seal_old,
+                "hp_mask": pa.chacha_hp_mask_batch, "open_old": pa.chacha_open_batch, "counters": pa.chacha_debug_counters,
+                "counters_field": "chacha_group_launches", "tool": "chacha_quic_rate", "bar_field": "bar"}
+
+    def seal_old(ks, hp_ks, recs, n, src, aad, out, hp, masks, sp):
+        pa.seal_batch_hp(ks, recs, n, src, aad, out, hp_ks, hp, masks, sp)
+
+    return {"keyset": lambda rng, n, zero_iv: pa.Keyset(rng.bytes(16 * n), bytes(12 * n) if zero_iv else rng.bytes(12 * n), 16),
+            "seal_new": pa.seal_quic_packets, "open_new": pa.open_quic_packets, "seal_old": seal_old,
+            "hp_mask": pa.hp_mask_batch, "open_old": pa.open_batch, "counters": pa.debug_counters,
+            "counters_field": "counters", "tool": "aesgcm_quic_rate", "bar_field": "aim"}
+
+
+def run_shape(suite: str, name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int, rounds: int) -> dict:
     import torch
 
     import picotls_amd as pa
     from picotls_amd.records import HP_DTYPE, QUIC_RESULT_DTYPE, RECORD_DTYPE
 
+    S = suite_calls(pa, suite)
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(9001)
     key_idx = (np.arange(n, dtype=np.uint32) * nkeys // n).astype(np.uint32)  # grouped by connection, as they arrive
@@ -62,8 +91,8 @@ def run_shape(name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int,
     pns = rng.integers(0, 2**62, n, dtype=np.uint64)
     slot = (1 + DCID + 4 + plen + 16 + 15) // 16 * 16
     off = np.arange(n, dtype=np.uint64) * np.uint64(slot)
-    ks = pa.ChaChaKeyset(rng.bytes(32 * nkeys), rng.bytes(12 * nkeys))
-    hp_ks = pa.ChaChaKeyset(rng.bytes(32 * nkeys), bytes(12 * nkeys))
+    ks = S["keyset"](rng, nkeys, False)
+    hp_ks = S["keyset"](rng, nkeys, True)
 
     # the cleartext packets, built on the device: header || payload in slots of `slot` bytes
     clear = torch.randint(0, 256, (n, slot), dtype=torch.uint8, device=dev)
@@ -100,19 +129,18 @@ def run_shape(name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int,
     sp = torch.cuda.current_stream(dev).cuda_stream
 
     def seal_new():
-        pa.chacha_seal_quic_packets(ks, hp_ks, d_seal_new.data_ptr(), n, clear.data_ptr(), d_wire.data_ptr(), sp)
+        S["seal_new"](ks, hp_ks, d_seal_new.data_ptr(), n, clear.data_ptr(), d_wire.data_ptr(), sp)
 
     def seal_old():
-        pa.chacha_seal_batch(ks, d_old.data_ptr(), n, clear.data_ptr(), clear.data_ptr(), d_sealed.data_ptr(), sp)
-        pa.chacha_hp_mask_batch(hp_ks, d_hp.data_ptr(), n, d_sealed.data_ptr(), d_masks.data_ptr(), sp)
+        S["seal_old"](ks, hp_ks, d_old.data_ptr(), n, clear.data_ptr(), clear.data_ptr(), d_sealed.data_ptr(), d_hp.data_ptr(),
+                      d_masks.data_ptr(), sp)
 
     def open_new():
-        pa.chacha_open_quic_packets(ks, hp_ks, d_open_new.data_ptr(), n, d_wire.data_ptr(), d_back.data_ptr(), d_ok.data_ptr(),
-                                    d_res.data_ptr(), sp)
+        S["open_new"](ks, hp_ks, d_open_new.data_ptr(), n, d_wire.data_ptr(), d_back.data_ptr(), d_ok.data_ptr(), d_res.data_ptr(), sp)
 
     def open_old():
-        pa.chacha_hp_mask_batch(hp_ks, d_hp.data_ptr(), n, d_wire.data_ptr(), d_masks.data_ptr(), sp)
-        pa.chacha_open_batch(ks, d_old.data_ptr(), n, d_wire.data_ptr(), clear.data_ptr(), d_back.data_ptr(), d_ok.data_ptr(), sp)
+        S["hp_mask"](hp_ks, d_hp.data_ptr(), n, d_wire.data_ptr(), d_masks.data_ptr(), sp)
+        S["open_old"](ks, d_old.data_ptr(), n, d_wire.data_ptr(), clear.data_ptr(), d_back.data_ptr(), d_ok.data_ptr(), sp)
 
     calls = {"seal": {"new": seal_new, "old": seal_old, "old_again": seal_old},
              "open": {"new": open_new, "old": open_old, "old_again": open_old}}
@@ -178,7 +206,7 @@ def run_shape(name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int,
         d["new_over_old"] = round(d["new"]["gib_per_s"] / d["old"]["gib_per_s"], 3)
         d["bar_met"] = d["new"]["gib_per_s"] >= d["old"]["gib_per_s"] * (1 - d["aa_spread"])
         out[direction] = d
-    out["chacha_group_launches"] = pa.chacha_debug_counters(reset=True)
+    out[S["counters_field"]] = S["counters"](reset=True)
     ks.free(), hp_ks.free()
     del clear, d_wire, d_sealed, d_back, d_masks, d_ok, d_res
     torch.cuda.empty_cache()
@@ -187,6 +215,7 @@ def run_shape(name: str, n: int, plen: int, nkeys: int, steps: int, warmup: int,
 
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--suite", choices=("aesgcm", "chacha"), required=True)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--rounds", type=int, default=5)
@@ -199,14 +228,15 @@ def main():
 
     assert torch.cuda.is_available(), "needs an MI355X"
     pa.load_library()
-    pa.chacha_debug_counters(reset=True)
+    S = suite_calls(pa, args.suite)
+    S["counters"](reset=True)
     shapes = []
     for name in [s for s in args.shapes.split(",") if s]:
         n, plen, nkeys = SHAPES[name]
         n = max(int(n * args.scale), 4)
-        shapes.append(run_shape(name, n, plen, min(nkeys, n), args.steps, args.warmup, args.rounds))
-    print(json.dumps({"tool": "chacha_quic_rate", "metric": "GiB/s over payload bytes, seal and open apart, device-resident",
-                      "shapes": shapes, "bar": "new >= old x (1 - A/A spread), seal and open, every shape",
+        shapes.append(run_shape(args.suite, name, n, plen, min(nkeys, n), args.steps, args.warmup, args.rounds))
+    print(json.dumps({"tool": S["tool"], "metric": "GiB/s over payload bytes, seal and open apart, device-resident",
+                      "shapes": shapes, S["bar_field"]: "new >= old x (1 - A/A spread), seal and open, every shape",
                       "bar_met": all(s[d]["bar_met"] for s in shapes for d in ("seal", "open")),
                       "verified": all(all(s["verified"].values()) for s in shapes)}))
 
