@@ -159,6 +159,30 @@ int ptls_mi355x_chacha_debug_poly1305(const void *key32, const void *msg, size_t
 int ptls_mi355x_chacha_debug_force(int group_lanes, int max_workgroups);
 int ptls_mi355x_chacha_debug_counters(uint64_t *out, int reset);
 
+/**
+ * Spread launches: an unframed batch of few records, and a per-record call with a long record, cut their long records
+ * into pieces that groups all over the device seal or open, and the last piece of a record to finish combines the
+ * pieces' Poly1305 partials into its tag. A record is cut into at most this many pieces; the piece length is the
+ * compiled base length doubled until that holds.
+ */
+#define PTLS_MI355X_CHACHA_SPREAD_MAX_PIECES 1024
+/**
+ * debug_spread: piece_bytes 0 = the compiled base piece length, else a multiple of 1024; min_len 0 = the compiled
+ * minimum lengths (records from that length are cut), else one value for batches and per-record calls alike; force
+ * nonzero = a group width forced with debug_force no longer keeps a batch or a call off the spread kernel. All zeros
+ * is automatic. Process-wide.
+ * debug_spread_counters: out[0] = spread launches, out[1] = pieces run, out[2] = records whose tag a combine finished,
+ * out[3] = whole (uncut) records run in spread launches. Waits for the device.
+ * debug_spread_params: out[0] = the minimum length in a batch, out[1] = on the per-record path, out[2] = the largest
+ * batch that takes a spread launch (records), out[3] = the base piece length.
+ * debug_rpow: r^e mod 2^130 - 5 with the device routine the pieces use, on HOST buffers: r16 = 16 little-endian bytes
+ * taken as they are (no clamp), out17 = the fully reduced result as 17 little-endian bytes.
+ */
+int ptls_mi355x_chacha_debug_spread(int piece_bytes, int min_len, int force);
+int ptls_mi355x_chacha_debug_spread_counters(uint64_t *out, int reset);
+int ptls_mi355x_chacha_debug_spread_params(uint32_t *out);
+int ptls_mi355x_chacha_debug_rpow(const void *r16, uint64_t e, void *out17);
+
 #ifdef __cplusplus
 }
 #endif

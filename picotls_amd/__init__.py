@@ -110,6 +110,10 @@ CHACHA_ABI_FUNCTIONS = (
     "ptls_mi355x_chacha_debug_poly1305",
     "ptls_mi355x_chacha_debug_force",
     "ptls_mi355x_chacha_debug_counters",
+    "ptls_mi355x_chacha_debug_spread",
+    "ptls_mi355x_chacha_debug_spread_counters",
+    "ptls_mi355x_chacha_debug_spread_params",
+    "ptls_mi355x_chacha_debug_rpow",
 )
 
 SIZE_MAX = ctypes.c_size_t(-1).value
@@ -208,6 +212,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.ptls_mi355x_chacha_debug_poly1305.argtypes = [vp, vp, sz, vp]
     lib.ptls_mi355x_chacha_debug_force.argtypes = [ci, ci]
     lib.ptls_mi355x_chacha_debug_counters.argtypes = [vp, ci]
+    lib.ptls_mi355x_chacha_debug_spread.argtypes = [ci, ci, ci]
+    lib.ptls_mi355x_chacha_debug_spread_counters.argtypes = [vp, ci]
+    lib.ptls_mi355x_chacha_debug_spread_params.argtypes = [vp]
+    lib.ptls_mi355x_chacha_debug_rpow.argtypes = [vp, u64, vp]
     _lib = lib
     return lib
 
@@ -535,6 +543,64 @@ def chacha_debug_counters(reset: bool = False) -> dict:
     if load_library().ptls_mi355x_chacha_debug_counters(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0) != 0:
         raise _err("ptls_mi355x_chacha_debug_counters")
     return dict(zip(CHACHA_GROUP_WIDTHS, (int(out[0]), int(out[1]))))
+
+
+CHACHA_SPREAD_MAX_PIECES = 1024  # PTLS_MI355X_CHACHA_SPREAD_MAX_PIECES: pieces a record is cut into at the most
+CHACHA_SPREAD_COUNTERS = ("launches", "pieces", "finished", "whole")
+
+
+def chacha_debug_spread(piece_bytes: int = 0, min_len: int = 0, force: bool = False) -> None:
+    """0, 0, False = automatic; otherwise the base piece length (a multiple of 1024), the length from which a record is
+    cut (batches and per-record calls alike) and whether a forced group width still lets a launch spread."""
+    if load_library().ptls_mi355x_chacha_debug_spread(piece_bytes, min_len, 1 if force else 0) != 0:
+        raise _err("ptls_mi355x_chacha_debug_spread")
+
+
+def chacha_debug_spread_counters(reset: bool = False) -> dict:
+    """Since the last reset: spread launches, pieces run, records finished by a combine, whole records run in spread
+    launches (CHACHA_SPREAD_COUNTERS). Waits for the device."""
+    out = (ctypes.c_uint64 * 4)()
+    if load_library().ptls_mi355x_chacha_debug_spread_counters(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0) != 0:
+        raise _err("ptls_mi355x_chacha_debug_spread_counters")
+    return dict(zip(CHACHA_SPREAD_COUNTERS, (int(x) for x in out)))
+
+
+def chacha_debug_spread_params() -> dict:
+    """The compiled tunables: min_batch / min_single (bytes from which a record is cut in a batch / on the per-record
+    path), max_recs (the largest batch that takes a spread launch), piece (the base piece length), max_pieces."""
+    out = (ctypes.c_uint32 * 4)()
+    if load_library().ptls_mi355x_chacha_debug_spread_params(ctypes.cast(out, ctypes.c_void_p)) != 0:
+        raise _err("ptls_mi355x_chacha_debug_spread_params")
+    return {"min_batch": int(out[0]), "min_single": int(out[1]), "max_recs": int(out[2]), "piece": int(out[3]),
+            "max_pieces": CHACHA_SPREAD_MAX_PIECES}
+
+
+def chacha_debug_rpow(r16: bytes, e: int) -> int:
+    """r^e mod 2^130 - 5 by the device's power routine, r the 16 little-endian bytes as they are
+    (ptls_mi355x_chacha_debug_rpow); the fully reduced result as an integer."""
+    if len(r16) != 16 or not 0 <= e < 2**64:
+        raise ValueError("r is 16 bytes and e fits 64 bits")
+    out = bytearray(17)
+    if load_library().ptls_mi355x_chacha_debug_rpow(_buf(bytes(r16)), e, _buf(out)) != 0:
+        raise _err("ptls_mi355x_chacha_debug_rpow")
+    return int.from_bytes(out, "little")
+
+
+def chacha_spread_plan(lens, params: dict) -> list:
+    """The cuts the device plan of a spread launch makes (pure Python): for each record length the list of its pieces'
+    (lo, hi) byte ranges, empty for a record that stays whole. params: "min_len" (records from this length are cut),
+    "piece" (the base piece length) and "max_pieces" (the piece length doubles until a record has no more than these)."""
+    plan = []
+    for n in lens:
+        n = int(n)
+        if n < max(int(params["min_len"]), 1) or n > 1 << 30:
+            plan.append([])
+            continue
+        piece = int(params["piece"])
+        while (n + piece - 1) // piece > int(params.get("max_pieces", CHACHA_SPREAD_MAX_PIECES)):
+            piece *= 2
+        plan.append([(lo, min(n, lo + piece)) for lo in range(0, n, piece)])
+    return plan
 
 
 # ------------------------------------------------------------------------------------------------ picotls mirror

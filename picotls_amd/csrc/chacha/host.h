@@ -6,6 +6,7 @@
 
 #define CHACHA_WG_PER_CU 4    // launch grid: this many 256-thread workgroups per CU at most (what ~120 VGPRs a lane keep resident)
 #define CHACHA_CLAIM_SLOTS 8  // claim counters per keyset: one per stream in use, shared in stream order beyond that
+#define CHACHA_SPREAD_WG_PER_CU 2  // grid of a spread launch of a batch (the host cannot count its pieces)
 
 // A keyset is the entry array and, behind it, its claim counters (a pair of u64 per slot, zero between launches).
 // Launches on one stream run in order and share a slot; a stream without one takes a free slot, or takes the least
@@ -16,6 +17,9 @@ struct st_ptls_mi355x_chacha_keyset_t {
     size_t nkeys = 0;
     ChaChaKey *d_keys = nullptr;
     unsigned long long *d_claim = nullptr;
+    // spread launches: per claim slot the records' accumulators (CHACHA_SPREAD_SCRATCH_BYTES, zero between launches),
+    // allocated in the order of the slot's stream on first use; a stream that takes a slot over waits as for the claim
+    unsigned long long *d_spread[CHACHA_CLAIM_SLOTS] = {};
     std::vector<uint8_t> ivs;  // the static IVs (get_iv reads these; the device copy is what seals use)
     std::mutex mu;             // launches from several threads: the two below, held from taking a slot through the
                                // launch and the use event after it
@@ -24,6 +28,7 @@ struct st_ptls_mi355x_chacha_keyset_t {
 };
 
 static std::atomic<u32> g_chacha_force_g{0}, g_chacha_force_wgs{0};
+static std::atomic<u32> g_chacha_spread_piece{0}, g_chacha_spread_min{0}, g_chacha_spread_force{0};  // debug_spread
 
 // `launch()` on `s` and the keyset's use after it (ks->mu held); a launch error is reported through `fmt`. A launch that
 // reads a second keyset too (QUIC packets: `hp_ks`, its mutex held as well) is a use of both.
@@ -71,6 +76,58 @@ static void chacha_launch_kernel(bool open, int frame, unsigned grid, hipStream_
         with_either<0, 1>(frame, go);
 }
 
+// the accumulators of claim slot `slot` for a spread launch on `s` (ks->mu held); nullptr on failure
+static unsigned long long *chacha_spread_scratch(ptls_mi355x_chacha_keyset_t *ks, unsigned slot, hipStream_t s)
+{
+    if (ks->d_spread[slot] == nullptr) {
+        void *p = nullptr;
+        if (hipMallocAsync(&p, CHACHA_SPREAD_SCRATCH_BYTES, s) != hipSuccess) {
+            (void)hipGetLastError();
+            fail("%s", "chacha spread: scratch allocation failed");
+            return nullptr;
+        }
+        if (hipMemsetAsync(p, 0, CHACHA_SPREAD_SCRATCH_BYTES, s) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFreeAsync(p, s);
+            fail("%s", "chacha spread: scratch setup failed");
+            return nullptr;
+        }
+        ks->d_spread[slot] = (unsigned long long *)p;
+    }
+    return ks->d_spread[slot];
+}
+
+// whether a launch may be a spread one: a forced group width keeps it on chacha_batch_kernel unless debug_spread forces
+static bool chacha_spread_allowed(u32 force_g) { return force_g == 0 || g_chacha_spread_force.load(std::memory_order_relaxed) != 0; }
+
+static u32 chacha_spread_base_piece(void)
+{
+    const u32 p = g_chacha_spread_piece.load(std::memory_order_relaxed);
+    return p != 0 ? p : CHACHA_SPREAD_PIECE;
+}
+
+static u32 chacha_spread_min_len(u32 compiled)
+{
+    const u32 m = g_chacha_spread_min.load(std::memory_order_relaxed);
+    return m != 0 ? m : compiled;
+}
+
+// the grid of a spread launch: the workgroups its pieces need where the host knows them (`want`, a lone record), at
+// most CHACHA_SPREAD_WG_PER_CU a CU
+static unsigned chacha_spread_grid(const DeviceState *ds, size_t want)
+{
+    size_t grid = std::min<size_t>(want, (size_t)ds->ncu * CHACHA_SPREAD_WG_PER_CU);
+    const u32 cap = g_chacha_force_wgs.load(std::memory_order_relaxed);
+    if (cap != 0)
+        grid = std::min<size_t>(grid, cap);
+    return (unsigned)std::max<size_t>(grid, 1);
+}
+
+static void chacha_launch_spread(bool open, unsigned grid, hipStream_t s, const ChaChaSpreadArgs &sa)
+{
+    with_bool(open, [&](auto OPEN) { chacha_spread_kernel<OPEN><<<grid, CHACHA_WG, 0, s>>>(sa); });
+}
+
 static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int frame, const ptls_mi355x_record_t *recs, size_t nrecs,
                                const void *in, const void *aad, void *out, uint8_t *ok, void *stream)
 {
@@ -87,6 +144,15 @@ static int chacha_launch_batch(ptls_mi355x_chacha_keyset_t *ks, bool open, int f
     ChaChaArgs a = {};
     a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
     a.recs = recs, a.nrecs = nrecs, a.in = (const uint8_t *)in, a.aad = (const uint8_t *)aad, a.out = (uint8_t *)out, a.ok = ok;
+    // a small unframed batch: its long records spread over the device (chacha_spread_kernel)
+    if (frame == 0 && nrecs <= CHACHA_SPREAD_MAX_RECS && chacha_spread_allowed(a.force_g)) {
+        ChaChaSpreadArgs sa = {};
+        sa.a = a, sa.piece = chacha_spread_base_piece(), sa.min_len = chacha_spread_min_len(CHACHA_SPREAD_MIN_BATCH);
+        if ((sa.acc = chacha_spread_scratch(ks, *slot, s)) == nullptr)
+            return -1;
+        const unsigned sgrid = chacha_spread_grid(ks->ds, SIZE_MAX);  // (the host cannot count the batch's pieces)
+        return chacha_launch_noted(ks, s, "chacha spread launch: %s", [&] { chacha_launch_spread(open, sgrid, s, sa); });
+    }
     a.claim = ks->d_claim + 2 * *slot;
     const unsigned grid = chacha_grid(ks->ds, nrecs);
     return chacha_launch_noted(ks, s, "chacha batch launch: %s", [&] { chacha_launch_kernel(open, frame, grid, s, a); });
@@ -172,6 +238,12 @@ void ptls_mi355x_chacha_keyset_free(ptls_mi355x_chacha_keyset_t *ks)
     if (std::lock_guard<std::mutex> lk(ks->mu); ks->uses.order_after_all(ds->maint) == 0 || ks->uses.drain()) {
         (void)hipMemsetAsync(ks->d_keys, 0, ks->nkeys * sizeof(ChaChaKey), ds->maint);
         free_after_maint(ds, ks->d_keys);
+        for (unsigned long long *p : ks->d_spread) {
+            if (p != nullptr) {
+                (void)hipMemsetAsync(p, 0, CHACHA_SPREAD_SCRATCH_BYTES, ds->maint);
+                free_after_maint(ds, p);
+            }
+        }
     }
     ks->uses.release(ds);
     clear_memory(ks->ivs.data(), ks->ivs.size());
@@ -307,7 +379,9 @@ int ptls_mi355x_chacha_hp_mask_batch(ptls_mi355x_chacha_keyset_t *hp_ks, const p
 
 }  // extern "C"
 
-// one record on host buffers: staged, sealed or opened by one launch of one workgroup on the stager's stream, copied back
+// one record on host buffers: staged, sealed or opened by one launch on the stager's stream, copied back. The launch is
+// one workgroup, or from CHACHA_SPREAD_MIN_SINGLE bytes a spread one of as many workgroups as the record's pieces need
+// (its accumulators are a claim slot's, in device memory: atomics on the mapped staging buffer would cross the bus).
 static int chacha_single(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, bool open, void *output, const ptls_mi355x_iovec_t *vec,
                          size_t incnt, size_t len, uint64_t seq, const void *aad, size_t aadlen, int *verified)
 {
@@ -319,7 +393,15 @@ static int chacha_single(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, bool o
     const size_t aad_at = 64, in_at = aad_at + ((aadlen + 63) & ~(size_t)63), in_len = len + (open ? 16 : 0);
     const size_t out_at = in_at + ((in_len + 63) & ~(size_t)63), out_len = len + (open ? 0 : 16);
     const size_t ok_at = out_at + ((out_len + 63) & ~(size_t)63), flag_at = ok_at + 16;
-    if (call.acquire(flag_at + 16) != 0)
+    const u32 force_g = g_chacha_force_g.load(std::memory_order_relaxed), base_piece = chacha_spread_base_piece();
+    const bool spread = len >= chacha_spread_min_len(CHACHA_SPREAD_MIN_SINGLE) && len <= PTLS_MI355X_MAX_RECORD_LEN &&
+                        aadlen <= PTLS_MI355X_MAX_AAD_LEN && chacha_spread_allowed(force_g);
+    unsigned nwg = 1;
+    if (spread) {
+        const u32 piece = chacha_spread_piece((u32)len, base_piece);
+        nwg = chacha_spread_grid(ks->ds, ((len + piece - 1) / piece + CHACHA_WG / CHACHA_G_WIDE - 1) / (CHACHA_WG / CHACHA_G_WIDE));
+    }
+    if (call.acquire(flag_at + (((size_t)nwg * 4 + 15) & ~(size_t)15)) != 0)
         return -1;
     uint8_t *h = call.host();
     ptls_mi355x_record_t rec = {};
@@ -330,20 +412,28 @@ static int chacha_single(ptls_mi355x_chacha_keyset_t *ks, size_t key_idx, bool o
         memcpy(h + aad_at, aad, aadlen);
     gather_iovec(h + in_at, vec, incnt);
     h[ok_at] = 0;
-    memset(h + flag_at, 0, 4);
+    memset(h + flag_at, 0, (size_t)nwg * 4);
     call.clear_lo = in_at, call.clear_hi = ok_at;
     uint8_t *d = call.dev();
     const hipStream_t s = call.stream();
     const u32 token = next_done_token();
     const int ret = call.roundtrip(out_at, [&] {
         ChaChaArgs a = {};
-        a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = g_chacha_force_g.load(std::memory_order_relaxed);
+        a.keys = ks->d_keys, a.nkeys = (u32)ks->nkeys, a.force_g = force_g;
         a.recs = (const ptls_mi355x_record_t *)d, a.nrecs = 1, a.in = d, a.aad = d, a.out = d, a.ok = d + ok_at;
-        a.claim = nullptr;  // one record, one workgroup: nothing to claim, so no claim slot either
+        a.claim = nullptr;  // one record: nothing to claim (a claim slot only for a spread launch's accumulators)
         a.done_flag = (u32 *)(d + flag_at), a.done_token = token;
         std::lock_guard<std::mutex> lk(ks->mu);
+        if (spread) {
+            const unsigned *slot = ks->slots.get(s, ks->uses, [&](unsigned &i) { return i = (unsigned)ks->slots.v.size(), true; });
+            ChaChaSpreadArgs sa = {};
+            sa.a = a, sa.piece = base_piece, sa.min_len = 1;  // (the length was weighed above)
+            if (slot == nullptr || (sa.acc = chacha_spread_scratch(ks, *slot, s)) == nullptr)
+                return -1;
+            return chacha_launch_noted(ks, s, "chacha single launch: %s", [&] { chacha_launch_spread(open, nwg, s, sa); });
+        }
         return chacha_launch_noted(ks, s, "chacha single launch: %s", [&] { chacha_launch_kernel(open, 0, 1, s, a); });
-    }, flag_at, 1, token);
+    }, flag_at, nwg, token);
     if (ret != 0)
         return -1;
     if (open) {
@@ -457,6 +547,63 @@ int ptls_mi355x_chacha_debug_force(int group_lanes, int max_workgroups)
         return fail("%s", "chacha debug_force: group_lanes is 0, 4 or 16 and max_workgroups is not negative");
     g_chacha_force_g.store((u32)group_lanes, std::memory_order_relaxed);
     g_chacha_force_wgs.store((u32)max_workgroups, std::memory_order_relaxed);
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_spread(int piece_bytes, int min_len, int force)
+{
+    if (piece_bytes < 0 || piece_bytes % 1024 != 0 || piece_bytes > (1 << 20) || min_len < 0)
+        return fail("%s", "chacha debug_spread: piece_bytes is 0 or a multiple of 1024 up to 2^20 and min_len is not negative");
+    g_chacha_spread_piece.store((u32)piece_bytes, std::memory_order_relaxed);
+    g_chacha_spread_min.store((u32)min_len, std::memory_order_relaxed);
+    g_chacha_spread_force.store(force != 0, std::memory_order_relaxed);
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_spread_counters(uint64_t *out, int reset)
+{
+    if (out == NULL)
+        return fail("%s", "chacha debug_spread_counters: invalid arguments");
+    HIP_TRY(hipDeviceSynchronize());  // (test-only) every launch made so far has counted itself
+    unsigned long long n[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyFromSymbol(n, HIP_SYMBOL(g_chacha_spread_stats), sizeof(n)));
+    for (int i = 0; i < 4; ++i)
+        out[i] = n[i], n[i] = 0;
+    if (reset)
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_chacha_spread_stats), n, sizeof(n)));
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_spread_params(uint32_t *out)
+{
+    if (out == NULL)
+        return fail("%s", "chacha debug_spread_params: invalid arguments");
+    out[0] = CHACHA_SPREAD_MIN_BATCH, out[1] = CHACHA_SPREAD_MIN_SINGLE, out[2] = CHACHA_SPREAD_MAX_RECS, out[3] = CHACHA_SPREAD_PIECE;
+    return 0;
+}
+
+int ptls_mi355x_chacha_debug_rpow(const void *r16, uint64_t e, void *out17)
+{
+    if (r16 == NULL || out17 == NULL)
+        return fail("%s", "chacha debug_rpow: invalid arguments");
+    DeviceState *ds = current_device_state();
+    if (ds == nullptr)
+        return -1;
+    StageCall call(ds);
+    // staging: [0, 16) r || [64, 81) the power
+    if (call.acquire(96) != 0)
+        return -1;
+    uint8_t *h = call.host();
+    memcpy(h, r16, 16);
+    uint8_t *d = call.dev();
+    const hipStream_t s = call.stream();
+    if (call.roundtrip(64, [&] {
+            chacha_rpow_kernel<<<1, 64, 0, s>>>(d, (u64)e, d + 64);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        }) != 0)
+        return -1;
+    memcpy(out17, h + 64, 17);
     return 0;
 }
 

@@ -429,6 +429,353 @@ __global__ __launch_bounds__(CHACHA_WG) void chacha_batch_kernel(ChaChaArgs a)
     publish_done(a.done_flag, a.done_token);
 }
 
+// ---- Spread launches: an unframed batch of a few records, or a lone long record, whose long records
+// are cut into pieces that 16-lane groups all over the device take, where chacha_batch_kernel gives a record of any
+// length to one group.
+//
+// Plan. Every workgroup derives the same plan from the descriptors (the host cannot read them): a record of min_len
+// bytes or more that chacha_record would not reject is cut into pieces of chacha_spread_piece() bytes, every other
+// record is one whole item for chacha_record at the width of chacha_batch_kernel's sample rule. Whole records are dealt
+// to the groups from the last workgroup down, pieces from the first up, by index: no workgroup waits for another.
+//
+// A piece [lo, hi) of the text is chacha_record's computation one level up: every lane runs block 0 for r (and s, which
+// only the finisher uses), lane j the keystream blocks lo / 64 + j, + 16, ..., folding its 16-byte blocks into its own
+// chain (stride r^61, then r^E to the piece's end); piece 0's lane 0 starts with the AAD. The group's sum times r^D,
+// D = the 16-byte text blocks behind the piece, is the piece's share of the tag polynomial:
+//     tag = ((sum_p partial_p r^D_p) + lenblock) r + s.
+//
+// Combine. The partials of a workgroup's neighbouring groups that belong to one record are added in LDS, and the sums go
+// as five 64-bit limb sums into the record's accumulator (atomic adds, nothing to carry below 2^38 summands), then a
+// fence, then the count of pieces: the workgroup whose count completes the record fences again, takes the sums with
+// atomic exchanges that leave zero behind, carries them into loose limbs and finishes the tag as chacha_record does. The
+// accumulators and counts are zero again when the launch ends.
+#define CHACHA_SPREAD_MAX_RECS 255u       // descriptors the plan reads: one per thread of a workgroup (the last stays free)
+#define CHACHA_SPREAD_PIECE 1024u         // bytes a piece: one step of a 16-lane group; doubled while a record has more
+#define CHACHA_SPREAD_MAX_PIECES PTLS_MI355X_CHACHA_SPREAD_MAX_PIECES  // ... pieces than this
+#define CHACHA_SPREAD_MIN_BATCH 1024u     // records from this length are cut: in a batch (100 x 1200 B 27.1 -> 22.9 us),
+#define CHACHA_SPREAD_MIN_SINGLE 1024u    // on the per-record path (1200 B 36.4 -> 25.6 us; profiles/chacha20_spread.md)
+#define CHACHA_SPREAD_ACC_WORDS 6         // per record: five limb sums and the count of its finished pieces
+#define CHACHA_SPREAD_SCRATCH_BYTES ((CHACHA_SPREAD_MAX_RECS + 1) * CHACHA_SPREAD_ACC_WORDS * sizeof(unsigned long long))
+
+struct ChaChaSpreadArgs {
+    ChaChaArgs a;  // claim is unused: the items are dealt by index
+    u32 piece;     // the piece length of records of up to piece x CHACHA_SPREAD_MAX_PIECES bytes (a multiple of 1024)
+    u32 min_len;   // records from this length are cut (at least 1)
+    unsigned long long *acc;  // CHACHA_SPREAD_ACC_WORDS per record, zero between launches
+};
+
+// [0] spread launches, [1] pieces run, [2] records finished by a combine, [3] whole records run in spread launches
+__device__ unsigned long long g_chacha_spread_stats[4];
+
+// the piece length of a record of len bytes: `base` doubled until at most CHACHA_SPREAD_MAX_PIECES pieces cover it
+__host__ __device__ inline u32 chacha_spread_piece(u32 len, u32 base)
+{
+    u64 p = base;
+    while (((u64)len + p - 1) / p > CHACHA_SPREAD_MAX_PIECES)
+        p <<= 1;
+    return (u32)p;
+}
+
+// Piece [lo, hi) of record r (not rejected; lo a multiple of 1024, hi its end or the text's) on a group of 16 lanes, j
+// the lane: crypts the bytes and returns, in every lane, the piece's share of the tag polynomial as a loose element.
+// otk: keystream block 0's first eight words (r || s).
+template <bool OPEN>
+__device__ __forceinline__ Fe chacha_piece(const ChaChaArgs &a, const ptls_mi355x_record_t &r, u32 lo, u32 hi, u32 j, u32 otk[8])
+{
+    constexpr u32 G = CHACHA_G_WIDE, STRIDE_E = 4 * G - 3;
+    constexpr int NBITS = __builtin_ctz(4 * G);
+    const u32 A = PTLS_MI355X_RECORD_AAD_LEN(&r), T = r.len;
+    const ChaChaKey *ke = a.keys + r.key_idx;
+    u32 key[8];
+    {
+        const u32x4 k0 = *(const u32x4 *)&ke->key[0], k1 = *(const u32x4 *)&ke->key[4];
+        key[0] = k0.x, key[1] = k0.y, key[2] = k0.z, key[3] = k0.w;
+        key[4] = k1.x, key[5] = k1.y, key[6] = k1.z, key[7] = k1.w;
+    }
+    const u32 n0 = ke->iv[0], n1 = ke->iv[1] ^ bswap32((u32)(r.seq >> 32)), n2 = ke->iv[2] ^ bswap32((u32)r.seq);
+    const uint8_t *src = a.in + r.in_off;
+    uint8_t *dst = a.out + r.out_off;
+    // 16-byte blocks of the text and up to the piece's end; the piece's 64-byte blocks [Cb0, Cb1)
+    const u32 C = (T + 15) >> 4, Cend = (hi + 15) >> 4, Cb0 = lo >> 6, Cb1 = (hi + 63) >> 6;
+
+    u32 x[16];
+    chacha20_block(key, 0, n0, n1, n2, x);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        otk[i] = x[i];
+    const Fe r1 = fe_clamped_r(otk[0], otk[1], otk[2], otk[3]);
+
+    // the lane's last block of the piece and the exponent E that aligns its partial with the piece's end
+    const u32 bf = Cb0 + j;
+    u32 E = 0;
+    if (bf < Cb1) {
+        const u32 blast = bf + ((Cb1 - 1 - bf) & ~(G - 1));
+        const u32 nblast = (min(64u, hi - 64 * blast) + 15) >> 4;
+        E = Cend - (4 * blast + nblast - 1);
+    }
+    Fe rE = fe_select((E & 1) != 0, r1, fe_one()), rS = r1, sq = r1;
+#pragma unroll
+    for (int bit = 1; bit < NBITS; ++bit) {
+        sq = fe_mul(sq, sq);
+        rE = fe_select(((E >> bit) & 1) != 0, fe_mul(rE, sq), rE);
+        if ((STRIDE_E >> bit) & 1)
+            rS = fe_mul(rS, sq);
+    }
+
+    Fe h = fe_zero();
+    if (lo == 0 && j == 0) {  // the owner of text block 0 starts with the AAD
+        const uint8_t *ap = a.aad + r.aad_off;
+        for (u32 off = 0; off < A; off += 16) {
+            const u32x4 w = load_upto16(ap + off, min(16u, A - off));
+            fe_add_block(h, w.x, w.y, w.z, w.w, 1), h = fe_mul(h, r1);
+        }
+    }
+    for (u32 b = bf; b < Cb1; b += G) {
+        chacha20_block(key, b + 1, n0, n1, n2, x);
+        const u32 o = 64 * b, nT = min(64u, hi - o);
+        u32x4 c[4];
+        if (nT == 64) {  // a whole block: four 16-byte accesses, nothing to clamp or mask
+#pragma unroll
+            for (u32 w = 0; w < 4; ++w) {
+                const u32x4 p = *(const u32x4_u *)(src + o + 16 * w);
+                const u32x4 ks = {x[4 * w], x[4 * w + 1], x[4 * w + 2], x[4 * w + 3]};
+                const u32x4 q = p ^ ks;
+                *(u32x4_u *)(dst + o + 16 * w) = q;
+                c[w] = OPEN ? p : q;
+            }
+        } else
+#pragma unroll
+        for (u32 w = 0; w < 4; ++w) {
+            const u32 nt = sub_clamp16(nT, 16 * w);
+            const u32x4 p = load_upto16(src + o + 16 * w, nt);
+            const u32x4 ks = {x[4 * w], x[4 * w + 1], x[4 * w + 2], x[4 * w + 3]};
+            const u32x4 q = p ^ ks;
+            store_upto16(dst + o + 16 * w, q, nt);
+            c[w] = OPEN ? p : keep_bytes(q, nt);  // the ciphertext, zero from its end
+        }
+        const u32 nb = (nT + 15) >> 4;
+        if (nb == 4 && b + G < Cb1) {
+            fe_add_block(h, c[0].x, c[0].y, c[0].z, c[0].w, 1), h = fe_mul(h, r1);
+            fe_add_block(h, c[1].x, c[1].y, c[1].z, c[1].w, 1), h = fe_mul(h, r1);
+            fe_add_block(h, c[2].x, c[2].y, c[2].z, c[2].w, 1), h = fe_mul(h, r1);
+            fe_add_block(h, c[3].x, c[3].y, c[3].z, c[3].w, 1), h = fe_mul(h, rS);
+        } else {  // the lane's last block of the piece (the only one that may be short)
+#pragma unroll
+            for (u32 t = 0; t < 4; ++t) {
+                if (t < nb) {
+                    fe_add_block(h, c[t].x, c[t].y, c[t].z, c[t].w, 1);
+                    h = fe_mul(h, fe_select(t + 1 < nb, r1, rE));
+                }
+            }
+        }
+    }
+    // the partials of the group, summed into all its lanes (every lane of the group is here), then carried over the
+    // C - Cend text blocks behind the piece
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+#pragma unroll
+        for (int m = 1; m < (int)G; m <<= 1)
+            h.v[i] += (u32)__shfl_xor((int)h.v[i], m, G);
+    }
+    return fe_mul(h, fe_pow(r1, C - Cend));
+}
+
+template <bool OPEN>
+__global__ __launch_bounds__(CHACHA_WG) void chacha_spread_kernel(ChaChaSpreadArgs sa)
+{
+    constexpr u32 NWAVES = CHACHA_WG / 64, GROUPS = CHACHA_WG / CHACHA_G_WIDE;
+    static_assert(CHACHA_SPREAD_MAX_RECS < CHACHA_WG, "one descriptor per thread");
+    __shared__ u32 s_len[NWAVES];
+    __shared__ u32 s_wave[2][NWAVES];     // the plan's scan: pieces and whole records per wave
+    __shared__ u32 s_incl[CHACHA_WG];     // pieces of the records [0, t]
+    __shared__ u32 s_whole[CHACHA_WG];    // the whole records, in batch order
+    __shared__ u32 s_rec[GROUPS];         // a round's partials: the record of each group's piece (none: ~0)
+    __shared__ u32 s_limb[GROUPS][5];
+    __shared__ u32 s_stat[2];             // pieces and whole records this workgroup ran
+    const ChaChaArgs &a = sa.a;
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid / 64, n = (u32)a.nrecs;
+
+    // the width of the whole records: chacha_batch_kernel's rule
+    u32 gw = a.force_g;
+    if (gw == 0) {
+        u32 len = min(a.recs[(u64)tid * a.nrecs / CHACHA_WG].len, PTLS_MI355X_MAX_RECORD_LEN >> 8);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1)
+            len += (u32)__shfl_xor((int)len, m);
+        if (lane == 0)
+            s_len[wave] = len;
+    }
+    // the plan: thread t reads descriptor t
+    u32 np = 0, wh = 0;
+    if (tid < n) {
+        const ptls_mi355x_record_t r = a.recs[tid];
+        const u32 A = PTLS_MI355X_RECORD_AAD_LEN(&r);
+        const bool good = r.len <= PTLS_MI355X_MAX_RECORD_LEN && A <= PTLS_MI355X_MAX_AAD_LEN && r.key_idx < a.nkeys &&
+                          (A == 0 || a.aad != nullptr);
+        if (good && r.len >= sa.min_len) {
+            const u32 piece = chacha_spread_piece(r.len, sa.piece);
+            np = (r.len + piece - 1) / piece;
+        } else {
+            wh = 1;
+        }
+    }
+    u32 ip = np, iw = wh;  // inclusive sums over the wave, then over the workgroup
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u32 tp = (u32)__shfl_up((int)ip, d), tw = (u32)__shfl_up((int)iw, d);
+        if (lane >= (u32)d)
+            ip += tp, iw += tw;
+    }
+    if (lane == 63)
+        s_wave[0][wave] = ip, s_wave[1][wave] = iw;
+    if (tid < 2)
+        s_stat[tid] = 0;
+    __syncthreads();
+    u32 totp = 0, totw = 0;
+#pragma unroll
+    for (u32 w = 0; w < NWAVES; ++w) {
+        if (w < wave)
+            ip += s_wave[0][w], iw += s_wave[1][w];
+        totp += s_wave[0][w], totw += s_wave[1][w];
+    }
+    s_incl[tid] = ip;
+    if (wh)
+        s_whole[iw - 1] = tid;
+    if (gw == 0) {
+        u32 sum = 0;
+#pragma unroll
+        for (u32 w = 0; w < NWAVES; ++w)
+            sum += s_len[w];
+        gw = sum / CHACHA_WG >= CHACHA_WIDE_MIN ? CHACHA_G_WIDE : CHACHA_G_NARROW;
+    }
+    __syncthreads();
+
+    // whole records: a round of the workgroup is CHACHA_WG / G of them, dealt from the last workgroup down
+    const auto whole = [&](auto GW) {
+        constexpr u32 G = decltype(GW)::value, PER_WAVE = 64 / G, PER_ROUND = CHACHA_WG / G;
+        for (u32 base = (gridDim.x - 1 - blockIdx.x) * PER_ROUND; base < totw; base += gridDim.x * PER_ROUND) {
+            const u32 k = base + wave * PER_WAVE + lane / G;
+            if (ENGINE_HOOKS && k < totw && lane % G == 0)
+                atomicAdd(&s_stat[1], 1u);
+            chacha_record<(int)G, OPEN, 0>(a, k < totw ? (u64)s_whole[k] : a.nrecs, lane % G);
+        }
+    };
+    if (gw == CHACHA_G_WIDE)
+        whole(std::integral_constant<u32, CHACHA_G_WIDE>{});
+    else
+        whole(std::integral_constant<u32, CHACHA_G_NARROW>{});
+
+    // pieces: a round is one per group, GROUPS consecutive ones a workgroup
+    const u32 g = tid / CHACHA_G_WIDE, j = tid % CHACHA_G_WIDE;
+    for (u32 base = blockIdx.x * GROUPS; base < totp; base += gridDim.x * GROUPS) {  // (the same trips in every group)
+        const u32 item = base + g;
+        const bool has = item < totp;
+        u32 t = ~0u, first = 0, otk[8] = {};
+        ptls_mi355x_record_t r = {};
+        Fe part = fe_zero();
+        if (has) {
+            u32 lo = 0, hi = n - 1;  // the record of the item: the first t with s_incl[t] > item
+            while (lo < hi) {
+                const u32 mid = (lo + hi) >> 1;
+                if (s_incl[mid] > item)
+                    hi = mid;
+                else
+                    lo = mid + 1;
+            }
+            t = lo, first = t != 0 ? s_incl[t - 1] : 0u;
+            r = a.recs[t];
+            const u32 piece = chacha_spread_piece(r.len, sa.piece), at = (item - first) * piece;
+            part = chacha_piece<OPEN>(a, r, at, min(r.len, at + piece), j, otk);
+            if (j == 0) {
+                s_rec[g] = t;
+#pragma unroll
+                for (int i = 0; i < 5; ++i)
+                    s_limb[g][i] = part.v[i];
+            }
+        } else if (j == 0) {
+            s_rec[g] = ~0u;
+        }
+        __syncthreads();
+        if (has && j == 0 && (g == 0 || s_rec[g - 1] != t)) {  // the first of the workgroup's groups on record t
+            unsigned long long sum[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+                sum[i] = part.v[i];
+            u32 run = 1;
+            for (u32 k = g + 1; k < GROUPS && s_rec[k] == t; ++k, ++run) {
+#pragma unroll
+                for (int i = 0; i < 5; ++i)
+                    sum[i] += s_limb[k][i];
+            }
+            if (ENGINE_HOOKS)
+                atomicAdd(&s_stat[0], run);
+            unsigned long long *acc = sa.acc + (size_t)CHACHA_SPREAD_ACC_WORDS * t;
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+                atomicAdd(acc + i, sum[i]);
+            __threadfence();  // the sums are visible device-wide before the count that publishes them
+            if (atomicAdd(acc + 5, (unsigned long long)run) + run == s_incl[t] - first) {
+                // these pieces completed the record: every other piece's sums are in (they were counted after a fence)
+                __threadfence();
+#pragma unroll
+                for (int i = 0; i < 5; ++i)
+                    sum[i] = atomicExch(acc + i, 0ull);  // (not a cached read; zero for the next launch)
+                atomicExch(acc + 5, 0ull);
+                // limb sums of up to CHACHA_SPREAD_MAX_PIECES loose elements: one carry pass in 64 bits leaves a loose one
+                sum[1] += sum[0] >> 26, sum[2] += sum[1] >> 26, sum[3] += sum[2] >> 26, sum[4] += sum[3] >> 26;
+                Fe h;
+                h.v[0] = ((u32)sum[0] & P26) + (u32)(sum[4] >> 26) * 5;  // (2^130 = 5; the carry out is small)
+#pragma unroll
+                for (int i = 1; i < 5; ++i)
+                    h.v[i] = (u32)sum[i] & P26;
+                const u32 A = PTLS_MI355X_RECORD_AAD_LEN(&r), T = r.len;
+                fe_add_block(h, A, 0, T, 0, 1);  // LE64(aadlen) || LE64(textlen)
+                h = fe_mul(h, fe_clamped_r(otk[0], otk[1], otk[2], otk[3]));
+                u32 tag[4];
+                fe_tag(h, &otk[4], tag);
+                if (OPEN) {
+                    // all 16 bytes compared, no early exit
+                    const u32x4 got = *(const u32x4_u *)(a.in + r.in_off + T);
+                    a.ok[t] = ((got.x ^ tag[0]) | (got.y ^ tag[1]) | (got.z ^ tag[2]) | (got.w ^ tag[3])) == 0;
+                } else {
+                    const u32x4 tg = {tag[0], tag[1], tag[2], tag[3]};
+                    *(u32x4_u *)(a.out + r.out_off + T) = tg;
+                }
+                if (ENGINE_HOOKS)
+                    atomicAdd(&g_chacha_spread_stats[2], 1ull);
+            }
+        }
+        __syncthreads();  // s_rec and s_limb are free again
+    }
+
+    if (ENGINE_HOOKS && tid == 0) {
+        if (blockIdx.x == 0) {
+            atomicAdd(&g_chacha_launches[gw == CHACHA_G_WIDE ? 1 : 0], 1ull);
+            atomicAdd(&g_chacha_spread_stats[0], 1ull);
+        }
+        if (s_stat[0] != 0)
+            atomicAdd(&g_chacha_spread_stats[1], (unsigned long long)s_stat[0]);
+        if (s_stat[1] != 0)
+            atomicAdd(&g_chacha_spread_stats[3], (unsigned long long)s_stat[1]);
+    }
+    publish_done(a.done_flag, a.done_token);
+}
+
+// Test hook (ptls_mi355x_chacha_debug_rpow): r^e on one lane with the pieces' power routine, fully reduced, as 17
+// little-endian bytes. r is the 16 bytes as they are (no clamp).
+__global__ __launch_bounds__(64) void chacha_rpow_kernel(const uint8_t *r16, u64 e, uint8_t *out17)
+{
+    if (threadIdx.x != 0)
+        return;
+    const u32x4 k = *(const u32x4_u *)r16;
+    Fe r = fe_zero();
+    fe_add_block(r, k.x, k.y, k.z, k.w, 0);
+    const Fe h = fe_reduced(fe_pow(r, e));
+    const u32x4 o = {h.v[0] | h.v[1] << 26, h.v[1] >> 6 | h.v[2] << 20, h.v[2] >> 12 | h.v[3] << 14, h.v[3] >> 18 | h.v[4] << 8};
+    *(u32x4_u *)out17 = o;
+    out17[16] = (uint8_t)(h.v[4] >> 24);
+}
+
 // QUIC header protection for the ChaCha20 suites: one lane per sample, one block. The sample's first 4 bytes are the
 // block counter (little endian) and the next 12 the nonce (picotls' 16-byte ChaCha20 IV, include/picotls.h:95); the mask
 // is the first 16 keystream bytes. An entry whose key_idx is out of range gets a zero mask.

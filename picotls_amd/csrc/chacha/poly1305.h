@@ -108,6 +108,36 @@ __device__ __forceinline__ void fe_tag(Fe h, const u32 s[4], u32 tag[4])
     tag[3] = (u32)f;
 }
 
+// h mod 2^130 - 5, every limb below 2^26 (the reduction fe_tag makes before it adds s). h loose (limbs below 2^31).
+__device__ __forceinline__ Fe fe_reduced(Fe h)
+{
+    fe_carry(h);
+    fe_carry(h);
+    fe_carry(h);
+    Fe g;
+    u32 c = 5;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        g.v[i] = h.v[i] + c;
+        c = g.v[i] >> 26;
+        g.v[i] &= P26;
+    }
+    return fe_select(c != 0, g, h);
+}
+
+// r^e by square and multiply from the low bit of e up: one squaring per bit up to e's highest set bit, and one
+// multiplication per bit whose result is selected, not branched on, as the kernels select rE. The trip count follows e,
+// which is a block count (public). r loose, loose out; e = 0 gives 1.
+__device__ __forceinline__ Fe fe_pow(const Fe &r, u64 e)
+{
+    Fe acc = fe_one(), sq = r;
+    for (; e != 0; e >>= 1) {
+        acc = fe_select((e & 1) != 0, fe_mul(acc, sq), acc);
+        sq = fe_mul(sq, sq);
+    }
+    return acc;
+}
+
 // r of a one-time key: the first 16 bytes clamped (RFC 8439 §2.5: r &= 0x0ffffffc0ffffffc0ffffffc0fffffff)
 __device__ __forceinline__ Fe fe_clamped_r(u32 k0, u32 k1, u32 k2, u32 k3)
 {

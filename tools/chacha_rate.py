@@ -11,7 +11,8 @@ workgroup 0 of every launch reads s_memtime and s_memrealtime at its start and e
 existing code: the yardstick, not the code under test. Prints one JSON line.
 
 Shapes: 131,072 x 16 KiB under one key; 1,048,576 x 1200 B under one key; 131,072 x 1200 B over 65,536 keys (2 a key).
-Also the per-record call latency (host buffers, one record a call) of both suites at 16 B, 1200 B and 16 KiB.
+Also the per-record call latency (host buffers, one record a call) of both suites at 16 B, 1200 B, 16 KiB, 64 KiB and
+1 MiB; --latency-libs times that call of several builds of the library against each other instead.
 
 Bar: chacha_over_aes >= 1.0 on every shape ("bar_met"). Measured (profiles/chacha20poly1305.md, builder-box): 1.25 on
 the 16 KiB shape, 10.8 on two packets per key, 0.93 (0.92 in earlier runs) on 2^20 x 1200 B under one key: that shape
@@ -124,6 +125,51 @@ def run_shape(name: str, nrecs: int, rec_len: int, nkeys: int, steps: int, warmu
     return out
 
 
+LATENCY_SIZES = (16, 1200, 16384, 65536, 1 << 20)
+
+
+def per_record_latency_libs(paths: list[str], calls: int = 300, rounds: int = 5, sizes=LATENCY_SIZES) -> dict:
+    """ptls_mi355x_chacha_encrypt of several builds of the library (a parent and a new one, or one twice for the noise),
+    interleaved in one process: `rounds` times each build in turn makes calls / rounds timed calls; the outputs are
+    compared. A path may be lib.so@PIECE:MIN_LEN (ptls_mi355x_chacha_debug_spread before each of its turns)."""
+    import ctypes
+
+    rng = np.random.default_rng(7)
+    key, iv, aad = rng.bytes(32), rng.bytes(12), b"0123456789abc"
+    vp, sz, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64
+    bound, arms = {}, []
+    for p in paths:
+        path, _, spread = p.partition("@")
+        if path not in bound:
+            lib = ctypes.CDLL(os.path.abspath(path))
+            lib.ptls_mi355x_chacha_keyset_new.argtypes, lib.ptls_mi355x_chacha_keyset_new.restype = [vp, vp, sz], vp
+            lib.ptls_mi355x_chacha_encrypt.argtypes = [vp, sz, vp, vp, sz, u64, vp, sz]
+            bound[path] = (lib, vp(lib.ptls_mi355x_chacha_keyset_new(key, iv, 1)))
+        arms.append((p, *bound[path], tuple(int(x) for x in spread.split(":")) if spread else None))
+    res = {p: {} for p in paths}
+    for n in sizes:
+        pt = rng.bytes(n)
+        outs = {p: ctypes.create_string_buffer(n + 16) for p in paths}
+        t = {p: [] for p in paths}
+        per = max(calls // rounds, 1)
+        for rnd in range(rounds + 1):  # (round 0 warms up)
+            for p, lib, ks, setting in arms:
+                if hasattr(lib, "ptls_mi355x_chacha_debug_spread"):  # (process-wide: a plain path is automatic)
+                    assert lib.ptls_mi355x_chacha_debug_spread(*(setting or (0, 0)), 0) == 0
+                for i in range(per if rnd else 20):
+                    t0 = time.perf_counter()
+                    rc = lib.ptls_mi355x_chacha_encrypt(ks, 0, outs[p], pt, n, i, aad, len(aad))
+                    dt = time.perf_counter() - t0
+                    assert rc == 0
+                    if rnd:
+                        t[p].append(dt)
+        same = all(outs[p].raw == outs[paths[0]].raw for p in paths)
+        for p in paths:
+            res[p][str(n)] = {"median_us": round(float(np.median(t[p])) * 1e6, 1), "p90_us": round(float(np.percentile(t[p], 90)) * 1e6, 1),
+                              "same_output": same}
+    return res
+
+
 def per_record_latency(calls: int = 300) -> dict:
     import picotls_amd as pa
 
@@ -133,7 +179,7 @@ def per_record_latency(calls: int = 300) -> dict:
     for name, algo in (("chacha20poly1305", pa.chacha20poly1305), ("aes256gcm", pa.aes256gcm)):
         ctx = pa.AeadContext(algo, True, key, iv)
         res[name] = {}
-        for n in (16, 1200, 16384):
+        for n in LATENCY_SIZES:
             pt = rng.bytes(n)
             for _ in range(20):
                 ctx.encrypt(pt, 1, b"0123456789abc")
@@ -155,7 +201,14 @@ def main():
     p.add_argument("--shapes", default="tls16k,quic1200,quic2perkey")
     p.add_argument("--scale", type=float, default=1.0, help="record counts times this (smaller runs)")
     p.add_argument("--no-latency", action="store_true")
+    p.add_argument("--latency-libs", nargs="+", default=None,
+                   help="only the per-record ChaCha20-Poly1305 latency of these builds, interleaved (per_record_latency_libs)")
+    p.add_argument("--latency-sizes", default="", help="record lengths for --latency-libs, comma separated")
     args = p.parse_args()
+    if args.latency_libs:
+        sizes = tuple(int(x) for x in args.latency_sizes.split(",")) if args.latency_sizes else LATENCY_SIZES
+        print(json.dumps({"tool": "chacha_rate", "per_record_encrypt_latency_libs": per_record_latency_libs(args.latency_libs, sizes=sizes)}))
+        return
     import torch
 
     import picotls_amd as pa
