@@ -122,11 +122,28 @@ int ptls_mi355x_keyset_set_iv(ptls_mi355x_keyset_t *ks, size_t key_idx, const vo
  *   CHUNKED   waves pull work units from a per-run queue. Runs of uniform record lengths use whole records as units;
  *             other runs cut records into 2 KiB GHASH units recombined with H^128, which balances mixed lengths and
  *             short per-connection key runs
+ *   RECORD_PER_LANE  (opt-in; AUTO never picks it) seal_batch, open_batch, seal_quic_packets and open_quic_packets run
+ *             one record per GPU lane. There is no per-key precomputation and no ordering requirement on key_idx:
+ *             records may come in any key order, no device grouping pass runs and no keyset scratch is taken. Meant
+ *             for large batches of short records over many keys (a QUIC server with many connections that flushes
+ *             often: one to eight packets per connection and batch); a record costs the same whatever the number of
+ *             records per key. The lanes of a wave run together, so a record longer than a few KiB holds its whole
+ *             wave for its duration. With this schedule len and the AAD length are limited to
+ *             PTLS_MI355X_LANE_MAX_LEN in those four calls: a record beyond the limit is rejected exactly as one
+ *             beyond PTLS_MI355X_MAX_RECORD_LEN is (nothing is written for it by the batch kernel; open reports
+ *             ok = 0). The cap exists because one lane works serially: without it a 1 GiB descriptor would occupy a
+ *             wave for minutes. Within the limit the output is byte-identical to every other schedule's. The kernel is
+ *             constant-time by its LDS layout, so constant-time keysets take it as set.
+ *             Every other call keeps the chunked kernels on a keyset set to this schedule, as under AUTO: the TLS 1.3
+ *             and TLS 1.2 framed calls, seal_batch_hp, the per-record host calls (encrypt, decrypt, encrypt_v,
+ *             encrypt_s), ECB, HP masks and QUIC-LB.
  * Returns 0, or -1 for an unknown schedule.
  */
 #define PTLS_MI355X_SCHEDULE_AUTO 0
 #define PTLS_MI355X_SCHEDULE_LOCKSTEP 1
 #define PTLS_MI355X_SCHEDULE_CHUNKED 2
+#define PTLS_MI355X_SCHEDULE_RECORD_PER_LANE 3
+#define PTLS_MI355X_LANE_MAX_LEN (1u << 16) /* len and AAD length of a record under RECORD_PER_LANE */
 int ptls_mi355x_keyset_set_schedule(ptls_mi355x_keyset_t *ks, int schedule);
 
 /**

@@ -16,9 +16,11 @@ extern "C" {
  *   out[0..4]  launches of the chunked batch kernel per instantiation: 0 plain (4-bit GHASH tables), 1 spread (small
  *              batch with long records), 2 seal with header-protection masks, 3 W8 long whole records (the second
  *              kernel of a W8 pair), 4 W8 serial (every other run of a W8 pair)
- *   out[5]     launches of the lockstep kernel, out[6] of the span kernels (a lone long record), out[7] 0
+ *   out[5]     launches of the lockstep kernel, out[6] of the span kernels (a lone long record), out[7] of the
+ *              record-per-lane kernel (PTLS_MI355X_SCHEDULE_RECORD_PER_LANE)
  *   out[8..12] runs processed on the device by each chunked instantiation (same order; a run skipped because the
- *              pair's other kernel takes it is not counted), out[13] 0, out[14] the EXT 4 runs among them that were
+ *              pair's other kernel takes it is not counted), out[13] the records the record-per-lane kernel accepted
+ *              (it has no runs; a rejected descriptor is not counted), out[14] the EXT 4 runs among them that were
  *              multi-key runs (round 6: several connections' short records in one run), out[15] the EXT 4 runs
  *              processed in 4-lane groups (whole runs of short records of one key)
  * Waits for the whole device (reading the device counters). reset != 0 zeroes them after reading. Returns 0 or -1.

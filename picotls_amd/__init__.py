@@ -300,10 +300,14 @@ class Keyset:
     def constant_time(self) -> bool:
         return bool(load_library().ptls_mi355x_keyset_get_constant_time(self.handle))
 
-    SCHEDULES = {"auto": 0, "lockstep": 1, "chunked": 2}
+    SCHEDULES = {"auto": 0, "lockstep": 1, "chunked": 2, "record_per_lane": 3}
 
     def set_schedule(self, schedule: str, allow_variable_time: bool = False) -> None:
-        """Batch schedule (ptls_mi355x_keyset_set_schedule): "auto", "lockstep" or "chunked".
+        """Batch schedule (ptls_mi355x_keyset_set_schedule): "auto", "lockstep", "chunked" or "record_per_lane".
+
+        "record_per_lane" (opt-in) runs seal_batch, open_batch and the QUIC packet calls one record per GPU lane, with no
+        per-key precomputation and no key order: for large batches of short records over many keys. Records and AADs are
+        then limited to PTLS_MI355X_LANE_MAX_LEN (64 KiB) in those calls; every other call runs as under "auto".
 
         The lockstep schedule (the round-1 kernel, kept for comparison) has data-dependent LDS bank conflicts, so the
         engine never runs it for a constant-time keyset (every keyset is one by default since round 4): the C call
@@ -777,7 +781,7 @@ def release_staging() -> None:
 # ------------------------------------------------------------------------------------------------ debug hooks
 
 
-COUNTER_NAMES = ("chunked", "spread", "seal_hp", "w8_tree", "w8_serial", "lockstep", "span", "w8_g4")
+COUNTER_NAMES = ("chunked", "spread", "seal_hp", "w8_tree", "w8_serial", "lockstep", "span", "lane")
 
 
 def debug_counters(reset: bool = False) -> dict:
@@ -789,7 +793,8 @@ def debug_counters(reset: bool = False) -> dict:
     runs = dict(zip(COUNTER_NAMES[:5], out[8:13]))
     runs["w8_g4"] = out[15]  # (of the w8_serial runs: whole runs in 4-lane groups)
     runs["w8_mk"] = out[14]  # (of the w8_serial runs: multi-key runs, round 6)
-    return {"launches": dict(zip(COUNTER_NAMES[:7], out[:7])), "runs": runs}
+    runs["lane_records"] = out[13]  # (the records the record-per-lane kernel accepted: it has no runs)
+    return {"launches": dict(zip(COUNTER_NAMES[:8], out[:8])), "runs": runs}
 
 
 def debug_inject_error() -> int:

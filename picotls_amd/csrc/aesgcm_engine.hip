@@ -58,6 +58,7 @@
 #include "engine/gcm_kernels.h"
 #include "quic/header.h"  // (suite-neutral: the ChaCha20 kernels below use it too)
 #include "engine/aux_kernels.h"
+#include "engine/lane_kernels.h"
 #include "engine/span_kernels.h"
 
 // ------------------------------------------------------------------------------------------------ host side

@@ -128,4 +128,20 @@ __device__ __forceinline__ void aes_ctr_cached1(const lds_u8 *lds, u32 laneoff, 
     aes_rounds_n<NR, 3, 1>(lds, laneoff, rk, s);
 }
 
+// ... of NB counter blocks of the cache's window at once (the record-per-lane kernel, lane_kernels.h: one wave per SIMD
+// keeps 16 * NB independent lookups in flight per round)
+template <int NR, int NB>
+__device__ __forceinline__ void aes_ctr_cached_n(const lds_u8 *lds, u32 laneoff, const u32 (*rk)[4], const CtrCache1 &c, u32 (&s)[NB][4])
+{
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        const u32 u0 = c.a0 ^ rotl8(te2(lds, s[i][3], 3, laneoff));
+        s[i][0] = c.b0 ^ te0(lds, u0, 0, laneoff);
+        s[i][1] = c.b1 ^ rotl8(te2(lds, u0, 3, laneoff));
+        s[i][2] = c.b2 ^ te2(lds, u0, 2, laneoff);
+        s[i][3] = c.b3 ^ rotl8(te0(lds, u0, 1, laneoff));
+    }
+    aes_rounds_n<NR, 3, NB>(lds, laneoff, rk, s);
+}
+
 #endif  // PTLS_MI355X_ENGINE_AES_TT_H

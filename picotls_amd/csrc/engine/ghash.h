@@ -520,4 +520,39 @@ __device__ __forceinline__ u32x4 w8_lane_end4(const lds_u8 *, u32x4 v, u32 lane,
     return group4_allreduce(group4_ws_terms(g, k, z));
 }
 
+// ------------------------------------------------------------------------------------------------ GHASH (one lane)
+//
+// The record-per-lane kernel (lane_kernels.h): t * H by one lane alone, Shoup's 4-bit method on the lane's own table
+// M[n] = n H (lds_tables.h build_lane_table, big-endian words, at mbase | n << 10). t is big-endian words (t[0] bits
+// 31..28 = the first nibble, x^0..x^3); Horner over its 32 nibbles from the last to the first,
+// Z = Z x^4 ^ M[nibble]: Z x^4 is a shift by 4 bits, and the 4 bits shifted out (x^124..x^127, now x^128..x^131) come
+// back times 1 + x + x^2 + x^7 at the top of word 0, in closed form as in gf_mulxs_be -- the "reduction table" R of the
+// method in registers, never a lookup by data. The 32 table addresses depend on t alone, so the loads issue ahead of
+// the chain on Z. Conflict-free for any data (the table's address map); no cross-lane step.
+__device__ __forceinline__ void gmul_lane(u32 mbase, const u32 (&t)[4], u32 (&z)[4])
+{
+    u32 z0 = 0, z1 = 0, z2 = 0, z3 = 0;
+#pragma unroll
+    for (int p = 31; p >= 0; --p) {
+        const u32 n = CT_PROBE_CONST ? 0u : (t[p >> 3] >> (28 - 4 * (p & 7))) & 15u;
+        const u32x4 e = lds_load128(mbase | n << 10);
+        if (p != 31) {
+            const u32 top = z3 << 28;
+            z3 = __builtin_amdgcn_alignbit(z2, z3, 4);
+            z2 = __builtin_amdgcn_alignbit(z1, z2, 4);
+            z1 = __builtin_amdgcn_alignbit(z0, z1, 4);
+            z0 = xor3(z0 >> 4, xor3(top, top >> 1, top >> 2), top >> 7);
+        }
+        z0 ^= e[0], z1 ^= e[1], z2 ^= e[2], z3 ^= e[3];
+    }
+    z[0] = z0, z[1] = z1, z[2] = z2, z[3] = z3;
+}
+
+// one serial Horner step Y = (Y ^ X) H; X as loaded from memory (LE words), Y big-endian words
+__device__ __forceinline__ void ghash_lane_fold(u32 mbase, u32 (&y)[4], u32x4 x)
+{
+    const u32 t[4] = {y[0] ^ bswap32(x[0]), y[1] ^ bswap32(x[1]), y[2] ^ bswap32(x[2]), y[3] ^ bswap32(x[3])};
+    gmul_lane(mbase, t, y);
+}
+
 #endif  // PTLS_MI355X_ENGINE_GHASH_H

@@ -224,4 +224,37 @@ __device__ __forceinline__ void build_elem_table_w4(lds_u8 *lds, u32 base, u32x4
     }
 }
 
+// The record-per-lane kernel's tables (lane_kernels.h): one private table per lane of the 16 4-bit multiples of its
+// record's hash key, M[n] = sum over the set bits of n of x^q H (bit 3 of n = x^0: a byte's high nibble, MSB first),
+// for Shoup's 4-bit multiply (ghash.h gmul_lane). Entry n of lane l of wave w sits at LANE_TAB_BASE + w * 16384 +
+// n * 1024 + l * 16: the bank quad of an address is 4 (l mod 16) whatever n, and the 16 lanes of each ds_read_b128
+// service group ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same above 32) hold the 16 values of l mod 16, so a
+// lookup indexed by data reads 16 disjoint bank quads for any nibbles; the 8 contiguous lanes of a ds_write_b128 phase
+// cover 32 distinct banks. Entries are big-endian words (the multiply shifts them), unlike the window tables above.
+#define LANE_TAB_BASE (u32)LDS_AES_BYTES
+#define LANE_LDS_BYTES (2 * LDS_AES_BYTES)
+__device__ __forceinline__ u32 lane_tab_base() { return LANE_TAB_BASE + (threadIdx.x >> 6) * 16384u + (threadIdx.x & 63u) * 16u; }
+
+// h: the hash key as stored in a KeyEntry (LE words)
+__device__ __forceinline__ void build_lane_table(lds_u8 *lds, u32 mbase, const u32 *h)
+{
+    u32 b0 = bswap32(h[0]), b1 = bswap32(h[1]), b2 = bswap32(h[2]), b3 = bswap32(h[3]);
+    u32x4 v[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        v[m] = u32x4{b0, b1, b2, b3};
+        if (m < 3)
+            gf_mulx_be(b0, b1, b2, b3);
+    }
+#pragma unroll
+    for (u32 n = 0; n < 16; ++n) {
+        u32x4 e = {0, 0, 0, 0};
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            if ((n >> (3 - m)) & 1u)
+                e ^= v[m];
+        *(lds_u32x4 *)(lds + mbase + n * 1024u) = e;
+    }
+}
+
 #endif  // PTLS_MI355X_ENGINE_LDS_TABLES_H

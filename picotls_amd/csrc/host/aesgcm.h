@@ -5,7 +5,7 @@
 #define PTLS_MI355X_HOST_AESGCM_H
 
 // Test and measurement counters (include/picotls/mi355x_debug.h): chunked-kernel launches per EXT instantiation (0..4),
-// lockstep launches (5), span launches (6) -- host side, counted where the launch is made
+// lockstep launches (5), span launches (6), record-per-lane launches (7) -- host side, counted where the launch is made
 static std::atomic<uint64_t> g_launches[8];
 #define COUNT_LAUNCH(i) (ENGINE_HOOKS ? g_launches[(i)].fetch_add(1, std::memory_order_relaxed) : 0)
 
@@ -63,7 +63,10 @@ static int set_kernel_attrs(void)
                     lds(LDS_AES_BYTES, quic_unmask_kernel<10>, quic_unmask_kernel<14>, quic_protect_kernel<10>,
                         quic_protect_kernel<14>) == 0 &&
                     lds(SPAN_LDS, gcm_span_kernel<10, false, true>, gcm_span_kernel<10, true, true>, gcm_span_kernel<14, false, true>,
-                        gcm_span_kernel<14, true, true>) == 0;
+                        gcm_span_kernel<14, true, true>) == 0 &&
+                    lds(LANE_LDS_BYTES, gcm_lane_kernel<10, false, 0>, gcm_lane_kernel<10, true, 0>, gcm_lane_kernel<14, false, 0>,
+                        gcm_lane_kernel<14, true, 0>, gcm_lane_kernel<10, false, 3>, gcm_lane_kernel<10, true, 3>,
+                        gcm_lane_kernel<14, false, 3>, gcm_lane_kernel<14, true, 3>) == 0;
     return ok ? 0 : -1;
 }
 
@@ -472,7 +475,7 @@ int ptls_mi355x_debug_wallclock_khz(void)
 
 int ptls_mi355x_keyset_set_schedule(ptls_mi355x_keyset_t *ks, int schedule)
 {
-    if (ks == NULL || schedule < PTLS_MI355X_SCHEDULE_AUTO || schedule > PTLS_MI355X_SCHEDULE_CHUNKED)
+    if (ks == NULL || schedule < PTLS_MI355X_SCHEDULE_AUTO || schedule > PTLS_MI355X_SCHEDULE_RECORD_PER_LANE)
         return fail("%s", "set_schedule: invalid arguments");
     ks->schedule = schedule;
     return 0;
@@ -554,6 +557,13 @@ static bool use_chunked(int schedule) { return schedule != PTLS_MI355X_SCHEDULE_
 // they predate the constant-time default and are kept as they are, deliberately, not by oversight.
 static bool runs_chunked(bool ct, int schedule) { return ct || use_chunked(schedule); }
 static bool runs_chunked(const ptls_mi355x_keyset_t *ks) { return runs_chunked(ks->ct, ks->schedule); }
+// The record-per-lane schedule (engine/lane_kernels.h) serves the unframed and QUIC-packet batch calls without
+// header-protection masks; every other call of a keyset set to it runs as under AUTO (use_chunked is true for it). It
+// is constant-time by layout, so a constant-time keyset takes it as set: it is not routed through runs_chunked.
+static bool runs_lane(int schedule, int frame, bool hp)
+{
+    return schedule == PTLS_MI355X_SCHEDULE_RECORD_PER_LANE && (frame == 0 || frame == 3) && !hp;
+}
 
 // Since the window-major segment ends the constant-time template argument changes no instruction of the chunked and
 // span kernels: every keyset, constant-time or not, launches the CT instantiation, the only one in the
@@ -663,6 +673,7 @@ struct GcmLaunch {
     const HpLaunch *hp;               // header-protection masks in the same launch (chunked seal of unframed records only)
     const ptls_mi355x_record_t *one;  // the descriptor of a batch of one: the chunked kernel takes it from its arguments
     uint8_t *spread;                  // the keyset's spread scratch, for a batch that may use it (spread_scratch_locked)
+    bool lane;                        // the record-per-lane kernel (launch_batch alone sets it: runs_lane)
 };
 
 static int launch_gcm(const GcmLaunch &g)
@@ -672,6 +683,22 @@ static int launch_gcm(const GcmLaunch &g)
     const u64 nrecs = a.nrecs;
     const bool chunked = runs_chunked(g.ct, g.schedule);
     a.multi_key = a.nkeys > 1 ? 1u : 0u;
+    if (g.lane) {
+        // one workgroup per CU, each walking tiles of LANE_WG records (no key runs, no scratch)
+        if (a.aad == NULL)
+            a.aad = a.in;
+        const u64 tiles = (nrecs + LANE_WG - 1) / LANE_WG;
+        const unsigned lgrid = (unsigned)(tiles < (u64)g.ncu ? tiles : (u64)g.ncu);
+        with_nr_open(g.nr, g.open, [&](auto NR, auto OPEN) {
+            COUNT_LAUNCH(7);
+            if (g.frame == 3)
+                gcm_lane_kernel<NR, OPEN, 3><<<lgrid, LANE_WG, LANE_LDS_BYTES, s>>>(a);
+            else
+                gcm_lane_kernel<NR, OPEN, 0><<<lgrid, LANE_WG, LANE_LDS_BYTES, s>>>(a);
+        });
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (g.hp != nullptr) {
         if (g.open || g.frame != 0 || !chunked)
             return fail("%s", "launch_gcm: header-protection masks need the chunked seal of unframed records");
@@ -827,7 +854,9 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
         return -1;
     LAUNCH_CLEAR();  // (the grouping kernels and launch_gcm's launch are checked after this)
     // ungrouped many-key batches: group the records by key on the device first (see key_hist_kernel)
-    const bool group = use_chunked(ks->schedule) && ks->nkeys > 1 && ks->nkeys <= KEY_GROUP_MAX_KEYS && nrecs > 1 &&
+    // (the record-per-lane schedule takes records in any key order: no grouping, no keyset scratch, ks->mu not taken for any)
+    const bool lane = runs_lane(ks->schedule, frame, hpl != nullptr);
+    const bool group = !lane && use_chunked(ks->schedule) && ks->nkeys > 1 && ks->nkeys <= KEY_GROUP_MAX_KEYS && nrecs > 1 &&
                        nrecs <= 0xffffffffu;
     // the keyset's scratch (spread pieces, key grouping) is shared by its launches on every stream: ks->mu is held from
     // taking it through the launch and the use event after it
@@ -838,12 +867,13 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
     g.a.keys = ks->d_keys, g.a.nkeys = (u32)ks->nkeys, g.a.recs = recs, g.a.nrecs = nrecs, g.a.unit_log2 = CHUNK_LOG2;
     g.a.in = (const uint8_t *)in, g.a.aad = (const uint8_t *)aad, g.a.out = (uint8_t *)out, g.a.ok = ok;
     g.stream = s, g.nr = ks->nr, g.ncu = ks->ds->ncu, g.schedule = ks->schedule, g.ct = ks->ct, g.open = open, g.frame = frame, g.hp = hpl;
+    g.lane = lane;
     // small batches with long records: the spread scratch
-    if (hpl == nullptr && spread_eligible(ks, nrecs, frame)) {
+    if (!lane && hpl == nullptr && spread_eligible(ks, nrecs, frame)) {
         if (!lk.owns_lock())
             lk.lock();
         g.spread = spread_scratch_locked(ks, s, nrecs);
-    } else if (hpl == nullptr && w8_eligible(ks, nrecs)) {  // (a spread launch never takes the W8 pair)
+    } else if (!lane && hpl == nullptr && w8_eligible(ks, nrecs)) {  // (a spread launch never takes the W8 pair)
         if (!lk.owns_lock())
             lk.lock();
         g.a.w8_flags = w8_flags_locked(ks, s);

@@ -4,6 +4,7 @@ key and payload, so that rocprofv3 --pmc SQ_LDS_BANK_CONFLICT / SQ_WAIT_INST_LDS
 be compared across keys and payloads. Identical shapes: record count, lengths, AAD, sequence numbers.
 
     python tools/ct_probe.py --key-seed 1 --payload zero|random|ones [--ct] [--workload tls16k --records 65536 --reps 3]
+                             [--schedule auto|lockstep|chunked|record_per_lane]
 """
 import argparse
 import os
@@ -25,6 +26,7 @@ def main():
     p.add_argument("--ct", action="store_true", help="the constant-time GHASH variant (ptls_mi355x_keyset_set_constant_time)")
     p.add_argument("--permute", type=int, default=0, help="seed of a permutation of the record lengths (0: none)")
     p.add_argument("--keys", type=int, default=0, help="override the workload's key count (0: keep it)")
+    p.add_argument("--schedule", default=None, help="the keyset's batch schedule (Keyset.set_schedule; default: as created)")
     p.add_argument("--no-check", action="store_true", help="skip the ok check (a CT_PROBE_CONST diagnosis build)")
     a = p.parse_args()
 
@@ -55,6 +57,8 @@ def main():
     ks = pa.Keyset(keys, ivs, wl.key_size)
     if a.ct:
         ks.set_constant_time(True)
+    if a.schedule:
+        ks.set_schedule(a.schedule, allow_variable_time=True)
     dev = torch.device("cuda:0")
     if a.payload == "random":
         d_pt = payload_torch(wl.seed, b.pt_bytes, dev)
@@ -74,7 +78,7 @@ def main():
     assert a.no_check or bool(d_ok.min().item() == 1)
     ks.free()
     print(f"ct_probe: key_seed={a.key_seed} payload={a.payload} workload={a.workload} records={b.n} ct={a.ct} "
-          f"permute={a.permute} keys={wl.nkeys} ok")
+          f"permute={a.permute} keys={wl.nkeys} schedule={a.schedule or 'default'} ok")
 
 
 if __name__ == "__main__":
