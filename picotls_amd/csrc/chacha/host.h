@@ -1,6 +1,6 @@
 // picotls_amd/csrc/chacha/host.h -- host side of the ChaCha20-Poly1305 engine: the C ABI of
 // include/picotls/mi355x_chacha20.h. Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip, included
-// last: built on host/runtime.h (per-device state, streams, event pool, StreamUses, StreamSlots, StageCall, error reporting).
+// last: built on host/runtime.h (per-device state, streams, event pool, StreamUses, Scratch, StreamSlots, StageCall, error reporting).
 #ifndef PTLS_MI355X_CHACHA_HOST_H
 #define PTLS_MI355X_CHACHA_HOST_H
 
@@ -18,8 +18,9 @@ struct st_ptls_mi355x_chacha_keyset_t {
     ChaChaKey *d_keys = nullptr;
     unsigned long long *d_claim = nullptr;
     // spread launches: per claim slot the records' accumulators (CHACHA_SPREAD_SCRATCH_BYTES, zero between launches),
-    // allocated in the order of the slot's stream on first use; a stream that takes a slot over waits as for the claim
-    unsigned long long *d_spread[CHACHA_CLAIM_SLOTS] = {};
+    // allocated in the order of the slot's stream on first use (Scratch); a stream that takes a slot over waits as for
+    // the claim
+    Scratch spread[CHACHA_CLAIM_SLOTS];
     std::vector<uint8_t> ivs;  // the static IVs (get_iv reads these; the device copy is what seals use)
     std::mutex mu;             // launches from several threads: the two below, held from taking a slot through the
                                // launch and the use event after it
@@ -76,25 +77,11 @@ static void chacha_launch_kernel(bool open, int frame, unsigned grid, hipStream_
         with_either<0, 1>(frame, go);
 }
 
-// the accumulators of claim slot `slot` for a spread launch on `s` (ks->mu held); nullptr on failure
+// the accumulators of claim slot `slot` for a spread launch on `s` (ks->mu held), all zero when allocated; nullptr on
+// failure, which fails the call
 static unsigned long long *chacha_spread_scratch(ptls_mi355x_chacha_keyset_t *ks, unsigned slot, hipStream_t s)
 {
-    if (ks->d_spread[slot] == nullptr) {
-        void *p = nullptr;
-        if (hipMallocAsync(&p, CHACHA_SPREAD_SCRATCH_BYTES, s) != hipSuccess) {
-            (void)hipGetLastError();
-            fail("%s", "chacha spread: scratch allocation failed");
-            return nullptr;
-        }
-        if (hipMemsetAsync(p, 0, CHACHA_SPREAD_SCRATCH_BYTES, s) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFreeAsync(p, s);
-            fail("%s", "chacha spread: scratch setup failed");
-            return nullptr;
-        }
-        ks->d_spread[slot] = (unsigned long long *)p;
-    }
-    return ks->d_spread[slot];
+    return (unsigned long long *)ks->spread[slot].take(ks->ds, ks->uses, s, CHACHA_SPREAD_SCRATCH_BYTES, CHACHA_SPREAD_SCRATCH_BYTES);
 }
 
 // whether a launch may be a spread one: a forced group width keeps it on chacha_batch_kernel unless debug_spread forces
@@ -238,12 +225,8 @@ void ptls_mi355x_chacha_keyset_free(ptls_mi355x_chacha_keyset_t *ks)
     if (std::lock_guard<std::mutex> lk(ks->mu); ks->uses.order_after_all(ds->maint) == 0 || ks->uses.drain()) {
         (void)hipMemsetAsync(ks->d_keys, 0, ks->nkeys * sizeof(ChaChaKey), ds->maint);
         free_after_maint(ds, ks->d_keys);
-        for (unsigned long long *p : ks->d_spread) {
-            if (p != nullptr) {
-                (void)hipMemsetAsync(p, 0, CHACHA_SPREAD_SCRATCH_BYTES, ds->maint);
-                free_after_maint(ds, p);
-            }
-        }
+        for (Scratch &acc : ks->spread)
+            acc.release(ds, true);
     }
     ks->uses.release(ds);
     clear_memory(ks->ivs.data(), ks->ivs.size());

@@ -89,31 +89,17 @@ struct st_ptls_mi355x_keyset_t {
     std::atomic<bool> pending;
     RawKey raw;
     std::vector<uint8_t> ivs;          // the static IVs (do_get_iv reads these; the device copy is what seals use)
-    std::mutex mu;                     // launches from several threads: uses, group scratch
+    std::mutex mu;                     // launches from several threads: uses and the scratch below
     StreamUses uses;                   // per stream: after this keyset's last launch on it
-    // key grouping of ungrouped many-key batches (key_group_*): scratch for key counts and the record permutation,
-    // grown on demand (stream-ordered); group_ev orders its users when batches on several streams share the keyset
-    u32 *d_group;
-    size_t group_cap;
-    hipEvent_t group_ev;
-    // small batches with long records (spread_pieces): the pieces' partials and per-record counters (zero
-    // between launches), allocated on first use; spread_stream: the stream of the last launch that used them (a launch
-    // on another stream waits for that one's use event)
-    uint8_t *d_spread;
-    size_t spread_cap;  // its bytes (sized for the batches seen so far, spread_bytes)
-    hipStream_t spread_stream;
-    bool spread_used;
+    // Scratch lent to launches on any stream (host/runtime.h Scratch), each grown to the largest batch seen so far:
+    Scratch group;   // ungrouped many-key batches (key_group_*): key counts, the record permutation, balance tiles
+    Scratch spread;  // small batches with long records (spread_pieces): per-record counters (zero between launches),
+                     // then the pieces' partials (spread_bytes)
+    Scratch quic;    // QUIC packets (launch_quic): the descriptors the pre-pass writes for the batch kernel
     // W8 launch pairs (launch_chunked): one word per workgroup from the pair's first kernel to its second,
     // one buffer per stream (allocated on the stream's first pair; a stream orders its own pairs), so that pairs on
     // several streams run concurrently; at most W8_FLAG_STREAMS (StreamSlots)
-    StreamSlots<u32 *, W8_FLAG_STREAMS> w8flags;
-    // QUIC packets (launch_quic): the descriptors the pre-pass writes for the batch kernel, grown on demand in stream
-    // order; quic_stream: the stream of the last call that used them (a call on another stream waits for that one's
-    // use event, as for the spread scratch)
-    ptls_mi355x_record_t *d_quic;
-    size_t quic_cap;  // its descriptors
-    hipStream_t quic_stream;
-    bool quic_used;
+    StreamSlots<Scratch, W8_FLAG_STREAMS> w8flags;
 };
 
 static int mark_ready(ptls_mi355x_keyset_t *ks, hipStream_t s);
@@ -183,8 +169,6 @@ static void keyset_destroy(ptls_mi355x_keyset_t *ks)
     DeviceState *ds = ks->ds;
     ks->uses.release(ds);
     event_put(ds, ks->ready);
-    if (ks->group_ev != nullptr)
-        (void)hipEventDestroy(ks->group_ev);
     clear_memory(ks->ivs.data(), ks->ivs.size());
     clear_memory(&ks->raw, sizeof(ks->raw));
     delete ks;
@@ -325,36 +309,29 @@ void ptls_mi355x_keyset_free(ptls_mi355x_keyset_t *ks)
     ks->pending.store(false, std::memory_order_release);  // never used: its setup never ran (the raw key is cleared below)
     // key material is cleared (ptls_clear_memory, lib/fusion.c:1045) after the keyset's last launch, on the maintenance
     // stream; nothing here waits on the host
-    bool ordered = !ds->fault_order && maint_after_uses(ks) == 0;
-    if (ks->group_ev != nullptr && hipStreamWaitEvent(ds->maint, ks->group_ev, 0) != hipSuccess)
-        ordered = false;
+    const bool ordered = !ds->fault_order && maint_after_uses(ks) == 0;
     if (!ordered) {
         // the teardown cannot be ordered after the keyset's launches on the device: wait for each of them (the recorded
-        // uses on every stream, the setup, the key grouping) on the host before clearing; if even that fails, keep the
-        // entries as they are and never reuse them, rather than clear them under a launch still reading them
+        // uses on every stream -- every launch that took scratch is among them -- and the setup) on the host before
+        // clearing; if even that fails, keep the entries and the scratch as they are and never reuse them, rather than
+        // clear them under a launch still reading them
         bool drained;
         {
             std::lock_guard<std::mutex> lk(ks->mu);
             drained = ks->uses.drain();
         }
         drained = hipEventSynchronize(ks->ready) == hipSuccess && drained;
-        if (ks->group_ev != nullptr)
-            drained = hipEventSynchronize(ks->group_ev) == hipSuccess && drained;
         if (!drained) {
             keyset_destroy(ks);
             return;
         }
     }
     (void)hipMemsetAsync(ks->d_keys, 0, ks->nkeys * sizeof(KeyEntry), ds->maint);
-    if (ks->d_group != nullptr)
-        (void)hipFreeAsync(ks->d_group, ds->maint);
-    if (ks->d_spread != nullptr)
-        (void)hipFreeAsync(ks->d_spread, ds->maint);
-    if (ks->d_quic != nullptr)
-        (void)hipFreeAsync(ks->d_quic, ds->maint);
+    ks->group.release(ds, false);
+    ks->spread.release(ds, false);
+    ks->quic.release(ds, false);
     for (auto &f : ks->w8flags.v)
-        (void)hipFreeAsync(f.second, ds->maint);
-    ks->w8flags.v.clear();
+        f.second.release(ds, false);
     if (ks->slot) {
         // back to the pool once the clear has run (slot_get checks the event)
         hipEvent_t cleared = event_get(ds);
@@ -672,7 +649,7 @@ struct GcmLaunch {
     int frame;
     const HpLaunch *hp;               // header-protection masks in the same launch (chunked seal of unframed records only)
     const ptls_mi355x_record_t *one;  // the descriptor of a batch of one: the chunked kernel takes it from its arguments
-    uint8_t *spread;                  // the keyset's spread scratch, for a batch that may use it (spread_scratch_locked)
+    uint8_t *spread;                  // the keyset's spread scratch, for a batch that may use it (launch_batch)
     bool lane;                        // the record-per-lane kernel (launch_batch alone sets it: runs_lane)
 };
 
@@ -761,6 +738,8 @@ static int launch_span(const GcmLaunch &g, u32 units, u32 e, u32 nspans, void *p
 }
 
 // (pieces of a record: at most its units / 2^10 + 1, 2^23 / SPREAD_UNIT_STEPS / 2^10 + 1 for the longest record)
+// Sized for the batch's records (16 B x (CUs + 1025 pieces per record), 164 KiB for 10 records instead
+// of 4.2 MB for the largest batch)
 static size_t spread_bytes(int ncu, size_t nrecs)
 {
     return SPREAD_CNT_BYTES + 16 * ((size_t)ncu + nrecs * (8192 / SPREAD_UNIT_STEPS + 1));
@@ -774,68 +753,17 @@ static bool spread_eligible(const ptls_mi355x_keyset_t *ks, size_t nrecs, int fr
 // a batch that may launch the W8 pair (launch_chunked): chunked, W8_MIN_RECS records
 static bool w8_eligible(const ptls_mi355x_keyset_t *ks, size_t nrecs) { return nrecs >= W8_MIN_RECS && runs_chunked(ks); }
 
-// orders a launch on `s` that uses the keyset's spread scratch after the last launch that used it;
-// the caller holds ks->mu from here through the launch and the use event recorded after it (launch_batch)
-static int scratch_order_locked(ptls_mi355x_keyset_t *ks, hipStream_t s)
-{
-    // a launch on another stream than the last user waits for that launch (its use event, recorded after it:
-    // launch_and_note); back-to-back launches on one stream add no event packets (a wait and a record per launch cost a
-    // 23 us small-batch launch 7 us)
-    if (ks->spread_used && ks->spread_stream != s) {
-        const hipEvent_t last = ks->uses.event_of(ks->spread_stream);
-        if (last != nullptr && hipStreamWaitEvent(s, last, 0) != hipSuccess)
-            return -1;
-    }
-    ks->spread_stream = s;
-    ks->spread_used = true;
-    return 0;
-}
-
 // the keyset's W8 flag words for a launch on `s`: the stream's own buffer (every word is written by the pair's first
 // kernel before its second reads it), allocated in stream order on the stream's first pair, or taken over (StreamSlots).
-// nullptr on failure: the pair then runs without them (EXT 3 scans every run). The caller holds ks->mu (launch_batch).
+// nullptr on failure: the pair then runs without them (EXT 3 scans every run). The caller holds ks->mu from here
+// through the launch and the use event recorded after it (launch_batch). (A takeover waits twice for the stream that
+// held the buffer, once for the slot and once for the block: the same event.)
 static u32 *w8_flags_locked(ptls_mi355x_keyset_t *ks, hipStream_t s)
 {
-    u32 **f = ks->w8flags.get(s, ks->uses, [&](u32 *&buf) {
-        return hipMallocAsync((void **)&buf, 4 * W8_FLAG_WORDS * (size_t)ks->ds->ncu, s) == hipSuccess;
-    });
-    if (f == nullptr) {
+    Scratch *f = ks->w8flags.get(s, ks->uses, [](Scratch &) { return true; });
+    if (f == nullptr)
         (void)hipGetLastError();
-        return nullptr;
-    }
-    return *f;
-}
-
-// the keyset's spread scratch for a launch on `s` (allocated and zeroed in stream order on first use); nullptr on
-// failure. The caller holds ks->mu from here through the launch and the use event recorded after it (launch_batch),
-// so a launch on another stream always finds the previous user's event recorded.
-static uint8_t *spread_scratch_locked(ptls_mi355x_keyset_t *ks, hipStream_t s, size_t nrecs)
-{
-    if (scratch_order_locked(ks, s) != 0)
-        return nullptr;
-    // sized for this batch's records (16 B x (CUs + 1025 pieces per record), 164 KiB for 10 records
-    // instead of 4.2 MB for the largest batch), grown in stream order when a batch needs more
-    const size_t bytes = spread_bytes(ks->ds->ncu, nrecs);
-    if (ks->d_spread != nullptr && ks->spread_cap < bytes) {
-        (void)hipFreeAsync(ks->d_spread, s);  // (ordered after its last user: scratch_order_locked)
-        ks->d_spread = nullptr;
-    }
-    if (ks->d_spread == nullptr) {
-        ks->spread_cap = 0;
-        if (hipMallocAsync((void **)&ks->d_spread, bytes, s) != hipSuccess) {
-            (void)hipGetLastError();
-            ks->d_spread = nullptr;
-            return nullptr;
-        }
-        if (hipMemsetAsync(ks->d_spread, 0, SPREAD_CNT_BYTES, s) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFreeAsync(ks->d_spread, s);
-            ks->d_spread = nullptr;
-            return nullptr;
-        }
-        ks->spread_cap = bytes;
-    }
-    return ks->d_spread;
+    return f != nullptr ? (u32 *)f->take(ks->ds, ks->uses, s, 4 * W8_FLAG_WORDS * (size_t)ks->ds->ncu) : nullptr;
 }
 
 // A batch call on a keyset: waits for the keyset's setup, groups an ungrouped many-key batch by key on the device, launches,
@@ -858,8 +786,10 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
     const bool lane = runs_lane(ks->schedule, frame, hpl != nullptr);
     const bool group = !lane && use_chunked(ks->schedule) && ks->nkeys > 1 && ks->nkeys <= KEY_GROUP_MAX_KEYS && nrecs > 1 &&
                        nrecs <= 0xffffffffu;
-    // the keyset's scratch (spread pieces, key grouping) is shared by its launches on every stream: ks->mu is held from
-    // taking it through the launch and the use event after it
+    // the keyset's scratch (spread pieces, W8 flags, key grouping) is shared by its launches on every stream: ks->mu is
+    // held from taking it (Scratch::take) through the launch and the use event after it. That event is
+    // recorded whether or not the launch succeeded (launch_and_note), so it stands behind the scratch's last user for the
+    // next stream that takes it, for a regrow and for teardown: the scratch needs no event of its own.
     // (launch_quic holds it already, around its own launches before and after this one: `held`, which stays locked)
     std::unique_lock<std::mutex> own(ks->mu, std::defer_lock);
     std::unique_lock<std::mutex> &lk = held != nullptr ? *held : own;
@@ -868,11 +798,12 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
     g.a.in = (const uint8_t *)in, g.a.aad = (const uint8_t *)aad, g.a.out = (uint8_t *)out, g.a.ok = ok;
     g.stream = s, g.nr = ks->nr, g.ncu = ks->ds->ncu, g.schedule = ks->schedule, g.ct = ks->ct, g.open = open, g.frame = frame, g.hp = hpl;
     g.lane = lane;
-    // small batches with long records: the spread scratch
+    // small batches with long records: the spread scratch, its counters zeroed when allocated (without it, the launch
+    // runs unspread)
     if (!lane && hpl == nullptr && spread_eligible(ks, nrecs, frame)) {
         if (!lk.owns_lock())
             lk.lock();
-        g.spread = spread_scratch_locked(ks, s, nrecs);
+        g.spread = (uint8_t *)ks->spread.take(ks->ds, ks->uses, s, spread_bytes(ks->ds->ncu, nrecs), SPREAD_CNT_BYTES);
     } else if (!lane && hpl == nullptr && w8_eligible(ks, nrecs)) {  // (a spread launch never takes the W8 pair)
         if (!lk.owns_lock())
             lk.lock();
@@ -887,18 +818,10 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
         const size_t gwords = ((2 + ks->nkeys + 1 + nrecs + 1) & ~(size_t)1) + nrecs * (sizeof(ptls_mi355x_record_t) / 4);
         const size_t twords = balance ? (ntiles + 1) & ~(size_t)1 : 0, bwords = balance ? 2 * (ncu + 1) : 0;
         const size_t nb = ks->nkeys + 1, words = gwords + twords + bwords;
-        if (ks->group_ev == NULL)
-            HIP_TRY(hipEventCreateWithFlags(&ks->group_ev, hipEventDisableTiming));
-        HIP_TRY(hipStreamWaitEvent(s, ks->group_ev, 0));  // a batch on another stream may still use the scratch
-        if (words > ks->group_cap) {  // grown in stream order on this stream (no device-wide free)
-            if (ks->d_group != NULL)
-                HIP_TRY(hipFreeAsync(ks->d_group, s));
-            ks->d_group = NULL;
-            ks->group_cap = 0;
-            HIP_TRY(hipMallocAsync((void **)&ks->d_group, words * 4, s));
-            ks->group_cap = words;
-        }
-        u32 *ctl = ks->d_group, *cnt = ctl + 2, *perm = cnt + nb;
+        u32 *ctl = (u32 *)ks->group.take(ks->ds, ks->uses, s, words * 4);
+        if (ctl == nullptr)
+            return -1;
+        u32 *cnt = ctl + 2, *perm = cnt + nb;
         HIP_TRY(hipMemsetAsync(ctl, 0, (2 + nb) * 4, s));
         const unsigned gh = (unsigned)min((nrecs + 255) / 256, (size_t)ks->ds->ncu * 8);
         key_changes_kernel<<<(unsigned)min((nrecs + 255) / 256, (size_t)ks->ds->ncu * KEY_CHANGES_WG_PER_CU), 256, 0, s>>>(recs, nrecs, ctl);
@@ -908,8 +831,8 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
         key_scatter_kernel<<<gh, 256, 0, s>>>(recs, nrecs, (u32)ks->nkeys, cnt, perm, grouped, ctl);
         u64 *bounds = nullptr;
         if (balance && use_chunked(ks->schedule)) {  // workgroup ranges of equal work (balance_bounds_kernel)
-            u32 *tiles = ks->d_group + gwords;
-            bounds = (u64 *)(ks->d_group + gwords + twords);
+            u32 *tiles = ctl + gwords;
+            bounds = (u64 *)(ctl + gwords + twords);
             const u32 grid = (u32)(ncu < nrecs ? ncu : nrecs);
             balance_tiles_kernel<<<(unsigned)min((ntiles + 3) / 4, ncu * 8), 256, 0, s>>>(recs, grouped, ctl + 1, nrecs, (u32)frame, tiles);
             balance_bounds_kernel<<<1, 1024, 0, s>>>(tiles, nrecs, grid, bounds);
@@ -917,9 +840,7 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
         g.a.grouped = grouped, g.a.perm = perm, g.a.perm_on = ctl + 1, g.a.bounds = bounds;
     }
     return launch_and_note(ks->uses, ks->ds, s, [&] {
-        int ret = launch_gcm(g);
-        if (ret == 0 && group && hipEventRecord(ks->group_ev, s) != hipSuccess)
-            ret = fail("%s", "hipEventRecord failed");
+        const int ret = launch_gcm(g);
         if (!lk.owns_lock())
             lk.lock();  // (a launch that took no scratch ran unlocked; the use is recorded under ks->mu)
         return ret;
@@ -952,7 +873,7 @@ static int launch_hp(const KeyEntry *keys, u32 nkeys, int nr, int ncu, const ptl
 
 // QUIC packets (ptls_mi355x_seal_quic_packets / ptls_mi355x_open_quic_packets): the pre-pass, the FRAME 3 batch on the
 // descriptors it wrote, the finish kernel (aux_kernels.h), all on `stream` with no host work between them. The
-// descriptors live in ks's scratch (d_quic), so ks->mu is held from taking it through the last launch and the use event
+// descriptors live in ks's scratch (Scratch quic), so ks->mu is held from taking it through the last launch and the use event
 // after it. The launches read both keysets: PairLock and launch_and_note_both (host/runtime.h).
 static int launch_quic(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, bool open, const ptls_mi355x_record_t *recs,
                        size_t nrecs, const void *in, void *out, uint8_t *ok, ptls_mi355x_quic_result_t *results, void *stream)
@@ -966,21 +887,9 @@ static int launch_quic(ptls_mi355x_keyset_t *ks, ptls_mi355x_keyset_t *hp_ks, bo
     if (wait_ready(ks, s) != 0 || (hp_ks != ks && wait_ready(hp_ks, s) != 0))
         return -1;
     PairLock<ptls_mi355x_keyset_t> locks(ks, hp_ks);
-    // the descriptor scratch: after its last user on another stream, grown in stream order on this one
-    if (ks->quic_used && ks->quic_stream != s) {
-        const hipEvent_t last = ks->uses.event_of(ks->quic_stream);
-        if (last != nullptr)
-            HIP_TRY(hipStreamWaitEvent(s, last, 0));
-    }
-    if (ks->quic_cap < nrecs) {
-        if (ks->d_quic != nullptr)
-            HIP_TRY(hipFreeAsync(ks->d_quic, s));
-        ks->d_quic = nullptr, ks->quic_cap = 0;
-        HIP_TRY(hipMallocAsync((void **)&ks->d_quic, nrecs * sizeof(ptls_mi355x_record_t), s));
-        ks->quic_cap = nrecs;
-    }
-    ks->quic_stream = s, ks->quic_used = true;
-    ptls_mi355x_record_t *desc = ks->d_quic;
+    ptls_mi355x_record_t *desc = (ptls_mi355x_record_t *)ks->quic.take(ks->ds, ks->uses, s, nrecs * sizeof(ptls_mi355x_record_t));
+    if (desc == nullptr)
+        return -1;
     const unsigned grid = aux_grid(nrecs, ks->ds->ncu);
     // (the kernels with the AES tables in LDS: two workgroups of QUIC_AUX_WG threads a CU)
     const unsigned lgrid = (unsigned)min((u64)(nrecs + QUIC_AUX_WG - 1) / QUIC_AUX_WG, (u64)ks->ds->ncu * 2);

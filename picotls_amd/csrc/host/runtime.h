@@ -1,6 +1,6 @@
 // picotls_amd/csrc/host/runtime.h -- the host runtime both AEAD families share: error reporting, the per-device state
 // and its pools (events, one-key slab entries, staging buffers), the synchronous staging round trip, the record of a
-// keyset's launches (StreamUses), per-stream slots (StreamSlots), the run-time -> template dispatch helpers and what a
+// keyset's launches (StreamUses), its scratch blocks (Scratch), per-stream slots (StreamSlots), the run-time -> template dispatch helpers and what a
 // call on two keysets needs (QUIC packets: argument check, PairLock, launch_and_note_both).
 // Part of the single translation unit picotls_amd/csrc/aesgcm_engine.hip (included after the device code; not standalone).
 #ifndef PTLS_MI355X_HOST_RUNTIME_H
@@ -108,7 +108,7 @@ struct DeviceState {
     unsigned stage_rr = 0;
     std::vector<std::pair<KeyEntry *, KeyEntry *>> slots;  // free one-key entries and the slab each lies in
     std::vector<PendingSlot> pending;
-    std::vector<std::pair<void *, hipEvent_t>> frees;  // freed keysets' entries until their clearing has run (free_after_maint)
+    std::vector<std::pair<void *, hipEvent_t>> frees;  // retired blocks until the event behind their last user has completed (retire_after)
     std::vector<hipEvent_t> events;
     int combine = 0;              // PTLS_MI355X_COMBINE: combined per-record launches in flight per kind (0: none)
     Combiner comb[32];
@@ -225,23 +225,25 @@ static void event_put(DeviceState *ds, hipEvent_t e)
     ds->events.push_back(e);
 }
 
-// The entries of a many-key keyset being freed, their clearing just queued on the maintenance stream: they go back to
-// the stream-ordered pool (hipFreeAsync) only once that has run, checked by the keyset calls that follow. hipFreeAsync on
-// the maintenance stream at once is not enough: the pool takes the stream a block was allocated on, the setup stream,
-// as safe for reuse without waiting, so the next keyset was handed the block and copied its keys into it while the
-// freed keyset's last launch was still reading it (tests/test_gpu_chacha.py, free and rekey right after a launch).
-static void free_after_maint(DeviceState *ds, void *entries)
+// Retires a block of stream-ordered memory whose last possible user is queued on `behind` (or ordered before what is):
+// an event is recorded there, and the block goes back to the pool (hipFreeAsync) only once that event has completed,
+// checked by the keyset calls that follow (`p` null: only that check). Nothing waits on the host. hipFreeAsync at
+// once is not enough, on whichever stream: the pool takes the stream a block was allocated on as safe for reuse
+// without waiting, so the next keyset was handed a block freed on the maintenance stream and copied its keys into it
+// while the freed keyset's last launch, on a third stream, was still reading it (tests/test_gpu_chacha.py, free and
+// rekey right after a launch).
+static void retire_after(DeviceState *ds, hipStream_t behind, void *p)
 {
     std::vector<void *> idle;
-    hipEvent_t cleared = entries != nullptr ? event_get(ds) : nullptr;
-    if (cleared != nullptr && hipEventRecord(cleared, ds->maint) != hipSuccess) {
-        event_put(ds, cleared);  // (the entries are kept, never reused, rather than freed under a launch)
-        cleared = nullptr;
+    hipEvent_t done = p != nullptr ? event_get(ds) : nullptr;
+    if (done != nullptr && hipEventRecord(done, behind) != hipSuccess) {
+        event_put(ds, done);  // (the block is kept, never reused, rather than freed under a launch)
+        done = nullptr;
     }
     {
         std::lock_guard<std::mutex> lk(ds->mu);
-        if (cleared != nullptr)
-            ds->frees.emplace_back(entries, cleared);
+        if (done != nullptr)
+            ds->frees.emplace_back(p, done);
         for (size_t i = 0; i < ds->frees.size();) {
             if (hipEventQuery(ds->frees[i].second) == hipSuccess) {
                 idle.push_back(ds->frees[i].first);
@@ -254,9 +256,12 @@ static void free_after_maint(DeviceState *ds, void *entries)
             }
         }
     }
-    for (void *p : idle)
-        (void)hipFreeAsync(p, ds->maint);
+    for (void *q : idle)
+        (void)hipFreeAsync(q, ds->maint);
 }
+
+// ... a freed keyset's entries, their clearing just queued on the maintenance stream
+static void free_after_maint(DeviceState *ds, void *entries) { retire_after(ds, ds->maint, entries); }
 
 // Which launches used a keyset: per stream it was used on, an event recorded after its last launch there. Teardown,
 // rekey and IV changes order themselves after all of them; a stream that takes over another stream's scratch or slot
@@ -311,6 +316,64 @@ static int launch_and_note(StreamUses &uses, DeviceState *ds, hipStream_t s, Lau
     memcpy(g_err, err, sizeof(err));
     return -1;
 }
+
+// A block of device scratch that a keyset lends to its launches on any stream: allocated in stream order by the first
+// launch that needs it, regrown when one needs more, retired with the keyset. Two rules keep it from being read and
+// written, or handed out again, under a launch still using it:
+//   * a launch on another stream than the last user's first waits for that stream's use event (StreamUses) -- so every
+//     launch that takes the block must be noted (launch_and_note) before the keyset's mutex is released; back-to-back
+//     launches on one stream add no event packets (a wait and a record per launch cost a 23 us small-batch launch 7 us);
+//   * a block outgrown (behind `s`, which by then waits for the last user) or released (behind the maintenance stream,
+//     ordered after every use) goes through retire_after, never to hipFreeAsync directly.
+// The keyset's mutex guards it, held from take() through the launch and its use event.
+struct Scratch {
+    void *p = nullptr;
+    size_t cap = 0;              // its bytes
+    hipStream_t last = nullptr;  // the stream of its last user (while p is set)
+    void retire(DeviceState *ds, hipStream_t behind)
+    {
+        if (p != nullptr)
+            retire_after(ds, behind, p);
+        p = nullptr, cap = 0;
+    }
+    // the block, of at least `bytes`, for a launch about to be made on `s`; a new block has its first `zero_prefix` bytes
+    // zeroed. nullptr after a HIP failure (the error text set), the owner then empty: the caller decides whether its
+    // launch can do without.
+    void *take(DeviceState *ds, const StreamUses &uses, hipStream_t s, size_t bytes, size_t zero_prefix = 0)
+    {
+        const auto failed = [&](hipStream_t behind, const char *what, hipError_t e) {
+            retire(ds, behind);
+            (void)hipGetLastError();  // (handled: the launches that follow are checked with hipGetLastError)
+            fail(what, hipGetErrorString(e));
+            return nullptr;
+        };
+        hipError_t e;
+        if (p != nullptr && last != s) {
+            const hipEvent_t used = uses.event_of(last);
+            if (used != nullptr && (e = hipStreamWaitEvent(s, used, 0)) != hipSuccess)
+                return failed(last, "scratch: hipStreamWaitEvent: %s", e);
+        }
+        if (bytes > cap) {
+            retire(ds, s);
+            if ((e = hipMallocAsync(&p, bytes, s)) != hipSuccess) {
+                p = nullptr;
+                return failed(s, "scratch: hipMallocAsync: %s", e);
+            }
+            if (zero_prefix != 0 && (e = hipMemsetAsync(p, 0, zero_prefix, s)) != hipSuccess)
+                return failed(s, "scratch: hipMemsetAsync: %s", e);
+            cap = bytes;
+        }
+        last = s;
+        return p;
+    }
+    // at teardown, the maintenance stream ordered after every use of the keyset (or the host having waited for them)
+    void release(DeviceState *ds, bool clear)
+    {
+        if (clear && p != nullptr)
+            (void)hipMemsetAsync(p, 0, cap, ds->maint);
+        retire(ds, ds->maint);
+    }
+};
 
 // At most CAP per-stream resources of a keyset (W8 flag buffers, ChaCha claim slots), most recently used last. A stream
 // runs its launches in order, so a stream's own entry needs no further ordering; a new stream beyond CAP takes over
