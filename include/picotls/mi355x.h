@@ -135,8 +135,9 @@ int ptls_mi355x_keyset_set_iv(ptls_mi355x_keyset_t *ks, size_t key_idx, const vo
  *             wave for minutes. Within the limit the output is byte-identical to every other schedule's. The kernel is
  *             constant-time by its LDS layout, so constant-time keysets take it as set.
  *             Every other call keeps the chunked kernels on a keyset set to this schedule, as under AUTO: the TLS 1.3
- *             and TLS 1.2 framed calls, seal_batch_hp, the per-record host calls (encrypt, decrypt, encrypt_v,
- *             encrypt_s), ECB, HP masks and QUIC-LB.
+ *             and TLS 1.2 framed calls and seal_batch_hp (unless ptls_mi355x_keyset_set_lane_framed, below, routes
+ *             them to the lane kernel too), the per-record host calls (encrypt, decrypt, encrypt_v, encrypt_s), ECB, HP
+ *             masks and QUIC-LB.
  * Returns 0, or -1 for an unknown schedule.
  */
 #define PTLS_MI355X_SCHEDULE_AUTO 0
@@ -145,6 +146,27 @@ int ptls_mi355x_keyset_set_iv(ptls_mi355x_keyset_t *ks, size_t key_idx, const vo
 #define PTLS_MI355X_SCHEDULE_RECORD_PER_LANE 3
 #define PTLS_MI355X_LANE_MAX_LEN (1u << 16) /* len and AAD length of a record under RECORD_PER_LANE */
 int ptls_mi355x_keyset_set_schedule(ptls_mi355x_keyset_t *ks, int schedule);
+/**
+ * A second opt-in beside the RECORD_PER_LANE schedule, off when a keyset is created: with on != 0, and while the
+ * keyset's schedule is RECORD_PER_LANE, seal_tls_records / open_tls_records, seal_tls12_records / open_tls12_records
+ * and seal_batch_hp run one record per GPU lane as well. It has no effect under any other schedule, may be set before or
+ * after set_schedule and survives a change of schedule. Meant for a TLS terminator with many connections that each
+ * flush one to eight small records per batch (or a QUIC sender that builds its own packets with seal_batch_hp).
+ *   The framed calls: the lane builds or checks the record header itself, the wire and plaintext bytes, ok bytes and
+ *             results are byte-identical to the chunked kernels' within PTLS_MI355X_LANE_MAX_LEN, and records may come
+ *             in any key order (no grouping pass, no keyset scratch). A record whose len is beyond the limit (or whose
+ *             key_idx is outside the keyset) is rejected as in the unframed lane calls: nothing is written for it, its
+ *             ok byte is 0, and the open calls therefore report PTLS_MI355X_TLS_BAD_MAC for it. As under every
+ *             schedule, only the unframed calls may seal or open in place: a framed record's input and output
+ *             ranges must not overlap (the wire record starts 5 or 13 bytes ahead of its text, so a lane's stores
+ *             would run into source bytes it has not loaded yet).
+ *   seal_batch_hp: two launches on the stream, the lane seal and then ptls_mi355x_hp_mask_batch over the sealed output,
+ *             so the masks are the same bytes for any sample_off, samples that cover a tag or a neighbouring record
+ *             included. The use of both keysets is recorded.
+ * set returns 0, or -1 for ks == NULL; get returns 1 when the setting is on, else 0.
+ */
+int ptls_mi355x_keyset_set_lane_framed(ptls_mi355x_keyset_t *ks, int on);
+int ptls_mi355x_keyset_get_lane_framed(const ptls_mi355x_keyset_t *ks);
 
 /**
  * Constant-time LDS access (no reference counterpart: fusion's AES-NI / PCLMUL code is constant-time by construction).

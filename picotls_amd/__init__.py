@@ -49,6 +49,8 @@ ABI_FUNCTIONS = (
     "ptls_mi355x_keyset_set_iv",
     "ptls_mi355x_keyset_update",
     "ptls_mi355x_keyset_set_schedule",
+    "ptls_mi355x_keyset_set_lane_framed",
+    "ptls_mi355x_keyset_get_lane_framed",
     "ptls_mi355x_keyset_set_constant_time",
     "ptls_mi355x_keyset_get_constant_time",
     "ptls_mi355x_seal_batch",
@@ -156,6 +158,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.ptls_mi355x_keyset_set_iv.argtypes = [vp, sz, vp]
     lib.ptls_mi355x_keyset_update.argtypes = [vp, vp, vp, vp, sz]
     lib.ptls_mi355x_keyset_set_schedule.argtypes = [vp, ci]
+    lib.ptls_mi355x_keyset_set_lane_framed.argtypes = [vp, ci]
+    lib.ptls_mi355x_keyset_get_lane_framed.argtypes = [vp]
+    lib.ptls_mi355x_keyset_get_lane_framed.restype = ci
     lib.ptls_mi355x_keyset_set_constant_time.argtypes = [vp, ci]
     lib.ptls_mi355x_keyset_get_constant_time.argtypes = [vp]
     lib.ptls_mi355x_keyset_get_constant_time.restype = ci
@@ -324,6 +329,17 @@ class Keyset:
             raise _err("set_schedule")
         if lockstep_ct:
             self.set_constant_time(False)
+
+    def set_lane_framed(self, on: bool = True) -> None:
+        """Under the "record_per_lane" schedule, run the TLS 1.3 and TLS 1.2 framed calls and seal_batch_hp one record
+        per GPU lane too (ptls_mi355x_keyset_set_lane_framed). Off on a new keyset; no effect under another schedule;
+        survives set_schedule. seal_batch_hp then makes two launches: the lane seal and hp_mask_batch."""
+        if load_library().ptls_mi355x_keyset_set_lane_framed(self.handle, 1 if on else 0) != 0:
+            raise _err("set_lane_framed")
+
+    @property
+    def lane_framed(self) -> bool:
+        return bool(load_library().ptls_mi355x_keyset_get_lane_framed(self.handle))
 
 
 def seal_batch(ks: Keyset, recs_ptr: int, nrecs: int, in_ptr: int, aad_ptr: int, out_ptr: int, stream: int = 0) -> None:

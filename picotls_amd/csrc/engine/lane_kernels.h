@@ -27,10 +27,14 @@ __device__ __forceinline__ bool lane_record_ok(const BatchArgs &args, const ptls
     return r.len <= PTLS_MI355X_LANE_MAX_LEN && gcm_aad_len<false, FRAME>(r) <= PTLS_MI355X_LANE_MAX_LEN && r.key_idx < args.nkeys;
 }
 
-// one accepted record, by one lane; i: its batch index (the ok byte)
+// one accepted record, by one lane; i: its batch index (the ok byte). The TLS framings (FRAME 1, 2: record.h) follow
+// gcm_segment byte for byte: the header or the 13-byte AAD is built in registers, a TLS 1.3 seal appends the content type
+// to the payload without reading the byte behind it, a framed open stores no plaintext under a header the record layer
+// refuses (wr) and computes the tag all the same. Every line of theirs is compiled for them alone.
 template <int NR, bool OPEN, int FRAME>
 __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, u32 laneoff, u32 mbase, const ptls_mi355x_record_t &r, u64 i)
 {
+    constexpr bool SEAL_FRAME = FRAME == 1 && !OPEN, TLS = FRAME == 1 || FRAME == 2, TLS12 = FRAME == 2, HDR = OPEN && TLS;
     const KeyEntry *k = args.keys + r.key_idx;
     u32 rk[NR + 1][4];
 #pragma unroll
@@ -39,21 +43,62 @@ __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, 
         for (int c = 0; c < 4; ++c)
             rk[q][c] = k->rk[q][c];
     build_lane_table(lds, mbase, k->h[0]);
-    // nonce = iv ^ (0^32 || BE64(seq)), as gcm_segment
+    // nonce = iv ^ (0^32 || BE64(seq)), as gcm_segment; TLS 1.2 takes the record's explicit nonce as stored in place of seq
+    u32 nw1 = bswap32((u32)(r.seq >> 32)), nw2 = bswap32((u32)r.seq);
+    if constexpr (TLS12) {
+        const uint8_t *e = args.in + r.in_off + (OPEN ? TLS_HEADER_SIZE : 0);
+        nw1 = *(const u32_u *)e;
+        nw2 = *(const u32_u *)(e + 4);
+    }
     const u32 n0 = k->iv[0] ^ rk[0][0];
-    const u32 n1 = k->iv[1] ^ bswap32((u32)(r.seq >> 32)) ^ rk[0][1];
-    const u32 n2 = k->iv[2] ^ bswap32((u32)r.seq) ^ rk[0][2];
+    const u32 n1 = k->iv[1] ^ nw1 ^ rk[0][1];
+    const u32 n2 = k->iv[2] ^ nw2 ^ rk[0][2];
 
-    const u32 A = gcm_aad_len<OPEN, FRAME>(r), L = r.len;
-    const uint8_t *src = args.in + r.in_off + quic_skip<FRAME>(A);
-    uint8_t *dst = args.out + r.out_off + quic_skip<FRAME>(A);
-    // (a QUIC packet's AAD is its header in the clear: the seal's input, or what the open's pre-pass left in the output)
-    const uint8_t *aadp = FRAME == 3 ? (OPEN ? (const uint8_t *)args.out + r.out_off : args.in + r.in_off) : args.aad + r.aad_off;
+    // (the text length through record.h's helper in the framed instantiations alone: read through it, r.len cost the
+    // unframed and QUIC kernels another register assignment, two SGPRs fewer, with no other change to their code)
+    const u32 A = gcm_aad_len<OPEN, FRAME>(r);
+    u32 L = r.len;
+    if constexpr (TLS)
+        L = gcm_text_len<OPEN, FRAME>(r);
+    // bytes of text readable at src (a TLS 1.3 seal reads len payload bytes; its last text byte is the content type)
+    const u32 Lsrc = SEAL_FRAME ? L - 1 : L;
+    const uint8_t *src = args.in + r.in_off + frame_in_skip<OPEN, FRAME>() + quic_skip<FRAME>(A);
+    uint8_t *dst = args.out + r.out_off + frame_out_skip<OPEN, FRAME>() + quic_skip<FRAME>(A);
+    // a framed open writes no plaintext under a header that tls_unpad_kernel / tls12_check_kernel refuse (segment.h)
+    bool wr = true;
+    if constexpr (HDR) {
+        const uint8_t *h = args.in + r.in_off;
+        const u32 w = *(const u32_u *)h, wl = (w >> 24) << 8 | h[4];
+        wr = FRAME == 1 ? (w & 0xffffffu) == 0x030317u && wl == L + 16
+                        : (w & 0xffff00u) == 0x030300u && wl == L + TLS12_RECORD_IV_SIZE + 16;
+    }
 
     u32 y[4] = {0, 0, 0, 0};
-    for (u32 o = 0; o < A; o += 16) {
-        const u32 rem = A - o;
-        ghash_lane_fold(mbase, y, rem >= 16 ? u32x4(*(const u32x4_u *)(aadp + o)) : load_partial(aadp + o, rem));
+    if constexpr (TLS) {  // one AAD block, from registers but for the TLS 1.3 open's, which is the header as received
+        u32x4 X;
+        if constexpr (SEAL_FRAME) {  // the record header: built here, written to the wire, and authenticated
+            const u32 wl = L + 16;
+            X = u32x4{0x00030317u | ((wl >> 8) & 0xffu) << 24, wl & 0xffu, 0, 0};
+            store_partial(args.out + r.out_off, X, TLS_HEADER_SIZE);
+        } else if constexpr (TLS12) {  // AAD = BE64(seq) || type || 3 || 3 || BE16(len) (build_tls12_aad)
+            const u32 type = OPEN ? (u32)args.in[r.in_off] : (r.flags & 0xffu);
+            X = u32x4{bswap32((u32)(r.seq >> 32)), bswap32((u32)r.seq), type | 0x030300u | ((L >> 8) & 0xffu) << 24, L & 0xffu};
+            if constexpr (!OPEN) {  // the wire header and the explicit nonce
+                const u32 wl = TLS12_RECORD_IV_SIZE + L + 16;
+                const u32x4 h = {type | 0x030300u | ((wl >> 8) & 0xffu) << 24, (wl & 0xffu) | nw1 << 8, nw1 >> 24 | nw2 << 8, nw2 >> 24};
+                store_partial(args.out + r.out_off, h, TLS_HEADER_SIZE + TLS12_RECORD_IV_SIZE);
+            }
+        } else {
+            X = load_partial(args.in + r.in_off, TLS_HEADER_SIZE);
+        }
+        ghash_lane_fold(mbase, y, X);
+    } else {
+        // (a QUIC packet's AAD is its header in the clear: the seal's input, or what the open's pre-pass left in the output)
+        const uint8_t *aadp = FRAME == 3 ? (OPEN ? (const uint8_t *)args.out + r.out_off : args.in + r.in_off) : args.aad + r.aad_off;
+        for (u32 o = 0; o < A; o += 16) {
+            const u32 rem = A - o;
+            ghash_lane_fold(mbase, y, rem >= 16 ? u32x4(*(const u32x4_u *)(aadp + o)) : load_partial(aadp + o, rem));
+        }
     }
 
     // Step s runs the counters 4s + 1 .. 4s + 4: E(K, J0) (counter 1) is slot 0 of step 0, text block b takes counter
@@ -66,7 +111,7 @@ __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, 
     for (u32 s = 0; s < nsteps; ++s) {
         const u32 c0 = 4 * s + 1;
         const int b0 = (int)(4 * s) - 1;  // slot 0's text block
-        const bool full = s != 0 && 16u * (u32)(b0 + 4) <= L;  // four whole text blocks
+        const bool full = s != 0 && 16u * (u32)(b0 + 4) <= Lsrc;  // four whole text blocks (of the readable source)
         // the step's input is loaded before any of its output is stored (out may alias in)
         u32x4 x[4];
         if (full) {
@@ -79,8 +124,12 @@ __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, 
                 const int b = b0 + q;
                 x[q] = u32x4{0, 0, 0, 0};
                 if (b >= 0 && b < (int)nb) {
-                    const u32 rem = L - 16u * (u32)b;
+                    const u32 rem = Lsrc - 16u * (u32)b;
                     x[q] = rem >= 16 ? u32x4(*(const u32x4_u *)(src + 16u * (u32)b)) : load_partial(src + 16u * (u32)b, rem);
+                    if constexpr (SEAL_FRAME) {  // the inner content type follows the payload (src[len] is never read)
+                        if (rem < 16)
+                            x[q][rem >> 2] |= (u32)(r.flags & 0xffu) << (8 * (rem & 3));
+                    }
                 }
             }
         }
@@ -102,7 +151,8 @@ __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const u32x4 o = x[q] ^ u32x4{st[q][0], st[q][1], st[q][2], st[q][3]};
-                *(u32x4_u *)(dst + 16u * (u32)(b0 + q)) = o;
+                if (!HDR || wr)
+                    *(u32x4_u *)(dst + 16u * (u32)(b0 + q)) = o;
                 if (!OPEN)
                     x[q] = o;
             }
@@ -117,10 +167,12 @@ __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, 
                     const u32 rem = L - 16u * (u32)b;
                     u32x4 o = x[q] ^ ks;
                     if (rem >= 16) {
-                        *(u32x4_u *)(dst + 16u * (u32)b) = o;
+                        if (!HDR || wr)
+                            *(u32x4_u *)(dst + 16u * (u32)b) = o;
                     } else {
                         o = mask_tail(o, rem);
-                        store_partial(dst + 16u * (u32)b, o, rem);
+                        if (!HDR || wr)
+                            store_partial(dst + 16u * (u32)b, o, rem);
                     }
                     if (!OPEN)
                         x[q] = o;
@@ -147,11 +199,12 @@ __device__ __forceinline__ void lane_record(const BatchArgs &args, lds_u8 *lds, 
     }
 }
 
-// FRAME 0 (unframed records) and 3 (QUIC packets: the descriptors are the pre-passes' rewritten ones, aux_kernels.h)
+// FRAME 0 (unframed records), 1 and 2 (TLS 1.3 and TLS 1.2 wire records, on a keyset with lane_framed set) and 3 (QUIC
+// packets: the descriptors are the pre-passes' rewritten ones, aux_kernels.h)
 template <int NR, bool OPEN, int FRAME>
 __global__ __launch_bounds__(LANE_WG) void gcm_lane_kernel(BatchArgs args)
 {
-    static_assert(FRAME == 0 || FRAME == 3, "unframed records and QUIC packets");
+    static_assert(FRAME >= 0 && FRAME <= 3, "unframed records, TLS 1.3 and TLS 1.2 wire records, QUIC packets");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     lds_u8 *lds = (lds_u8 *)smem;
     check_lds_base(smem);

@@ -66,7 +66,10 @@ static int set_kernel_attrs(void)
                         gcm_span_kernel<14, true, true>) == 0 &&
                     lds(LANE_LDS_BYTES, gcm_lane_kernel<10, false, 0>, gcm_lane_kernel<10, true, 0>, gcm_lane_kernel<14, false, 0>,
                         gcm_lane_kernel<14, true, 0>, gcm_lane_kernel<10, false, 3>, gcm_lane_kernel<10, true, 3>,
-                        gcm_lane_kernel<14, false, 3>, gcm_lane_kernel<14, true, 3>) == 0;
+                        gcm_lane_kernel<14, false, 3>, gcm_lane_kernel<14, true, 3>) == 0 &&
+                    lds(LANE_LDS_BYTES, gcm_lane_kernel<10, false, 1>, gcm_lane_kernel<10, true, 1>, gcm_lane_kernel<14, false, 1>,
+                        gcm_lane_kernel<14, true, 1>, gcm_lane_kernel<10, false, 2>, gcm_lane_kernel<10, true, 2>,
+                        gcm_lane_kernel<14, false, 2>, gcm_lane_kernel<14, true, 2>) == 0;
     return ok ? 0 : -1;
 }
 
@@ -81,6 +84,7 @@ struct st_ptls_mi355x_keyset_t {
     bool slot;  // d_keys is one entry of the device's slab (one-key keysets)
     KeyEntry *slab;  // ... that slab
     int schedule;
+    bool lane_framed;                  // under RECORD_PER_LANE the TLS-framed calls and seal_batch_hp take the lane kernel too
     bool ct;                           // constant-time GHASH (ptls_mi355x_keyset_set_constant_time)
     hipEvent_t ready;                  // the last setup / update / set_iv of the entries
     std::atomic<bool> ready_seen;      // ... known to be complete: launches need not wait for it
@@ -458,6 +462,16 @@ int ptls_mi355x_keyset_set_schedule(ptls_mi355x_keyset_t *ks, int schedule)
     return 0;
 }
 
+int ptls_mi355x_keyset_set_lane_framed(ptls_mi355x_keyset_t *ks, int on)
+{
+    if (ks == NULL)
+        return fail("%s", "set_lane_framed: invalid arguments");
+    ks->lane_framed = on != 0;
+    return 0;
+}
+
+int ptls_mi355x_keyset_get_lane_framed(const ptls_mi355x_keyset_t *ks) { return ks != NULL && ks->lane_framed ? 1 : 0; }
+
 int ptls_mi355x_keyset_set_constant_time(ptls_mi355x_keyset_t *ks, int on)
 {
     if (ks == NULL)
@@ -535,11 +549,13 @@ static bool use_chunked(int schedule) { return schedule != PTLS_MI355X_SCHEDULE_
 static bool runs_chunked(bool ct, int schedule) { return ct || use_chunked(schedule); }
 static bool runs_chunked(const ptls_mi355x_keyset_t *ks) { return runs_chunked(ks->ct, ks->schedule); }
 // The record-per-lane schedule (engine/lane_kernels.h) serves the unframed and QUIC-packet batch calls without
-// header-protection masks; every other call of a keyset set to it runs as under AUTO (use_chunked is true for it). It
-// is constant-time by layout, so a constant-time keyset takes it as set: it is not routed through runs_chunked.
-static bool runs_lane(int schedule, int frame, bool hp)
+// header-protection masks and, on a keyset with lane_framed set (ptls_mi355x_keyset_set_lane_framed), the TLS 1.3 and
+// TLS 1.2 framed calls (seal_batch_hp then makes two launches and passes no masks here); every other call of a keyset
+// set to it runs as under AUTO (use_chunked is true for it). It is constant-time by layout, so a constant-time keyset
+// takes it as set: it is not routed through runs_chunked.
+static bool runs_lane(int schedule, bool lane_framed, int frame, bool hp)
 {
-    return schedule == PTLS_MI355X_SCHEDULE_RECORD_PER_LANE && (frame == 0 || frame == 3) && !hp;
+    return schedule == PTLS_MI355X_SCHEDULE_RECORD_PER_LANE && (frame == 0 || frame == 3 || lane_framed) && !hp;
 }
 
 // Since the window-major segment ends the constant-time template argument changes no instruction of the chunked and
@@ -670,6 +686,10 @@ static int launch_gcm(const GcmLaunch &g)
             COUNT_LAUNCH(7);
             if (g.frame == 3)
                 gcm_lane_kernel<NR, OPEN, 3><<<lgrid, LANE_WG, LANE_LDS_BYTES, s>>>(a);
+            else if (g.frame == 2)
+                gcm_lane_kernel<NR, OPEN, 2><<<lgrid, LANE_WG, LANE_LDS_BYTES, s>>>(a);
+            else if (g.frame == 1)
+                gcm_lane_kernel<NR, OPEN, 1><<<lgrid, LANE_WG, LANE_LDS_BYTES, s>>>(a);
             else
                 gcm_lane_kernel<NR, OPEN, 0><<<lgrid, LANE_WG, LANE_LDS_BYTES, s>>>(a);
         });
@@ -783,7 +803,7 @@ static int launch_batch(ptls_mi355x_keyset_t *ks, bool open, const ptls_mi355x_r
     LAUNCH_CLEAR();  // (the grouping kernels and launch_gcm's launch are checked after this)
     // ungrouped many-key batches: group the records by key on the device first (see key_hist_kernel)
     // (the record-per-lane schedule takes records in any key order: no grouping, no keyset scratch, ks->mu not taken for any)
-    const bool lane = runs_lane(ks->schedule, frame, hpl != nullptr);
+    const bool lane = runs_lane(ks->schedule, ks->lane_framed, frame, hpl != nullptr);
     const bool group = !lane && use_chunked(ks->schedule) && ks->nkeys > 1 && ks->nkeys <= KEY_GROUP_MAX_KEYS && nrecs > 1 &&
                        nrecs <= 0xffffffffu;
     // the keyset's scratch (spread pieces, W8 flags, key grouping) is shared by its launches on every stream: ks->mu is
@@ -1026,7 +1046,9 @@ int ptls_mi355x_seal_batch_hp(ptls_mi355x_keyset_t *ks, const ptls_mi355x_record
         return fail("%s", "seal_batch_hp: the keysets are on different devices");
     if (nrecs == 0)
         return 0;
-    if (!runs_chunked(ks)) {  // the lockstep schedule: the seal, then the masks (a second launch)
+    // the lockstep schedule, or the record-per-lane one on a keyset with lane_framed set: the seal, then the masks (a
+    // second launch on the stream, which reads the sealed bytes wherever the sample lies; each call records its keyset's use)
+    if (!runs_chunked(ks) || (ks->schedule == PTLS_MI355X_SCHEDULE_RECORD_PER_LANE && ks->lane_framed)) {
         if (launch_batch(ks, false, recs, nrecs, in, aad, out, NULL, stream) != 0)
             return -1;
         return ptls_mi355x_hp_mask_batch(hp_ks, hp, nrecs, out, masks, stream);
